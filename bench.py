@@ -7,13 +7,19 @@ partitions). A "step" is one reduce_by_key pass over the batch already
 resident in HBM (H2D/generation is untimed; collect is untimed — the
 PCIe-inclusive rate is discussed in DESIGN.md).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N>1 is launched by the driver via torch.distributed.run, one rank per GPU;
    ranks read RANK/LOCAL_RANK/WORLD_SIZE from the env. Scaling is WEAK: each
    rank processes its own --rows shard of the global stream; the exchange is
    the counts-all-to-all + all-to-all-v over RCCL/xGMI.)
 
-Rank 0 prints ONE JSON line per the contract, plus:
+A plain run sets up, warms up, times the K steps and prints the result line
+(`ms_per_step` = milliseconds per timed step). --dump-outputs DIR then also
+writes what the LAST timed step returned to DIR/<name>.npy (see dump_outputs).
+Inputs are a pure function of the arguments, so two builds can be compared
+output for output.
+
+Rank 0 prints ONE JSON line per the contract; with --full it also fills in:
   roofline     — dominant kernel (radix_scatter) achieved GB/s vs the 8 TB/s
                  HBM peak, measured with HIP events on the launch stream
                  during the timed region (algorithmic bytes: DESIGN.md §Roofline)
@@ -88,6 +94,48 @@ def read_traffic_calibration(rows):
     return None
 
 
+DUMP_SAMPLE_ROWS = 1 << 20   # rows kept per output array (<= 64 MB in all)
+DUMP_SAMPLE_SEED = 0x5EED
+
+
+def dump_outputs(dirpath, outs, nout, f64_values, rank, world):
+    """Write the arrays the last timed step handed back as DIR/<name>.npy.
+
+    `outs` is the step's ((name, device tensor), ...) and `nout` the number of
+    valid leading rows in each. Outputs longer than DUMP_SAMPLE_ROWS are
+    sampled at a fixed, seeded, ascending set of row indices (a function of
+    nout only), so the same build and arguments give the same files. All
+    files are float64: an int64 column is split into `<name>_hi` / `<name>_lo`
+    (signed upper / unsigned lower 32 bits, both exact in float64; value =
+    hi * 2**32 + lo), an f64-sum value column is written as is. `nout.npy`
+    holds the row count. Ranks other than 0 append `.rank<r>` to each name.
+    """
+    import torch
+    os.makedirs(dirpath, exist_ok=True)
+    sfx = f".rank{rank}" if world > 1 and rank else ""
+
+    def save(name, arr):
+        np.save(os.path.join(dirpath, f"{name}{sfx}.npy"),
+                np.ascontiguousarray(arr, dtype=np.float64))
+
+    nout = int(nout)
+    idx = None
+    if nout > DUMP_SAMPLE_ROWS:
+        rng = np.random.default_rng(DUMP_SAMPLE_SEED)
+        idx = np.sort(rng.integers(0, nout, size=DUMP_SAMPLE_ROWS, dtype=np.int64))
+        idx = torch.from_numpy(idx).to(outs[0][1].device)
+    for name, t in outs:
+        t = t[:nout]
+        h = (t.index_select(0, idx) if idx is not None else t).cpu()
+        if f64_values and name == "values":
+            save(name, h.view(torch.float64).numpy())
+        else:
+            a = h.numpy()
+            save(name + "_hi", a >> 32)
+            save(name + "_lo", a & 0xFFFFFFFF)
+    save("nout", np.array([nout]))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -97,7 +145,16 @@ def main():
                     help="rows per GPU (weak scaling)")
     ap.add_argument("--key-bits", type=int, default=63)
     ap.add_argument("--seed", type=int, default=0xC0FFEE + 1)  # config C1
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs "
+                         "to DIR/<name>.npy (float64; sampled above "
+                         f"{DUMP_SAMPLE_ROWS} rows)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: "
+                         "per-kernel stats + roofline of the timed steps and "
+                         "the CPU-oracle baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU-oracle baseline leg")
     ap.add_argument("--op", choices=["reduce", "group_count", "sort", "join"],
                     default="reduce",
                     help="reduce = C1 (driver default); group_count = C2 "
@@ -113,6 +170,8 @@ def main():
                     "hardware coverage of the collective plumbing on a "
                     "1-GPU box (launch via torch.distributed.run)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
 
     import torch
     from vega_amd import gpu, shuffle
@@ -160,9 +219,11 @@ def main():
         pv = torch.empty(rows, dtype=torch.int64, device=dev)
 
     nout = None
+    outs = None   # ((name, tensor), ...) the last step returned; rows [:nout]
 
     def step_reduce(op):
-        nonlocal nout
+        nonlocal nout, outs
+        outs = (("keys", out_k), ("values", out_v))
         if not dist_on:
             nout = gpu.dev_sort_reduce(k, v, op, out_k, out_v, ws)
         else:
@@ -176,7 +237,8 @@ def main():
         # C2 with map-side pre-combine (vega's own map-side combine,
         # dependency.rs:191-210): local (key,count) aggregate BEFORE the
         # exchange, so Zipf hot keys cross xGMI as one row per rank
-        nonlocal nout
+        nonlocal nout, outs
+        outs = (("keys", out_k), ("values", out_v))
         if not dist_on:
             nout = gpu.dev_sort_reduce(k, v, gpu.OP_COUNT, out_k, out_v, ws)
             return
@@ -187,12 +249,13 @@ def main():
         nout = gpu.dev_sort_reduce(rk, rv, gpu.OP_SUM_I64, out_k, out_v, ws)
 
     def step_sort():
-        nonlocal nout
+        nonlocal nout, outs
         if not dist_on:
             out_k[:rows].copy_(k)
             out_v[:rows].copy_(v)
             gpu.dev_sort_pairs(out_k[:rows], out_v[:rows], ws)
             nout = rows
+            outs = (("keys", out_k), ("values", out_v))
         else:
             spl = shuffle.choose_splitters(k, world)
             counts = gpu.dev_partition_range(k, v, spl, pk, pv, ws)
@@ -201,6 +264,7 @@ def main():
                 raise RuntimeError(f"recv shard {rk.numel()} > cap {cap}")
             gpu.dev_sort_pairs(rk, rv, ws)
             nout = rk.numel()
+            outs = (("keys", rk), ("values", rv))
 
     if args.op == "join":
         # C4: second side, keys uniform in [0, rows) both sides
@@ -233,7 +297,8 @@ def main():
         return gpu.dev_join_grouped(ak_t, av_t, bk_t, bv_t, 0, jk, jva, jvb, ws)
 
     def step_join():
-        nonlocal nout
+        nonlocal nout, outs
+        outs = (("keys", jk), ("values_a", jva), ("values_b", jvb))
         if not dist_on:
             out_k[:rows].copy_(k); out_v[:rows].copy_(v)
             sb_k[:rows].copy_(kb); sb_v[:rows].copy_(vb)
@@ -264,7 +329,7 @@ def main():
         step()
     barrier_sync()
 
-    profiling = (rank == 0 and not dist_on)
+    profiling = (args.full and rank == 0 and not dist_on)
     if profiling:
         gpu.prof_enable(True)
 
@@ -306,6 +371,10 @@ def main():
             }
         log(f"[rank 0] kernel stats: {json.dumps(stats)}")
 
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, outs, nout,
+                     args.op == "reduce" and args.dtype == "f64", rank, world)
+
     if rank == 0:
         out = {
             "metric": METRIC,
@@ -314,7 +383,7 @@ def main():
             "n_gpus": n_gpus,
             "steps": args.steps,
             "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 2),
+            "ms_per_step": round(ms_per_step, 4),
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,  # reference publishes no numbers
@@ -331,7 +400,8 @@ def main():
             },
             "roofline": roofline,
             "cpu_baseline": (cpu_baseline_leg(rows, args.key_bits, args.seed)
-                             if (world == 1 and not args.no_cpu_baseline) else None),
+                             if (args.full and world == 1
+                                 and not args.no_cpu_baseline) else None),
         }
         print(json.dumps(out), flush=True)
 
