@@ -171,6 +171,46 @@ int vega_gpu_collect_join(vega_ctx_t *ctx, vega_rdd_t rdd, int64_t *keys,
 int vega_gpu_collect_groups(vega_ctx_t *ctx, vega_rdd_t rdd, int64_t *keys,
                             uint64_t *offsets, void *values, uint64_t *nk,
                             uint64_t *nvals);
+/* ---- device-side actions: only the answer crosses to the host ----
+ * All take plain pair handles only (grouped / join-result handles:
+ * VEGA_ERR_INVALID; ngpus > 1 context: VEGA_ERR_UNSUPPORTED) and never
+ * modify the input. A plain element RDD is encoded as in distinct: element
+ * in the key column, value column 0. */
+/* reduce (rdd.rs:274-291) with the closure |(k1,v1),(k2,v2)| (k1 op k2,
+ * v1 op v2): op in {SUM_I64, SUM_F64, MIN_I64, MAX_I64} applied column-wise.
+ * The key column is always i64 (SUM wraps, also under SUM_F64); out_v is
+ * int64_t or double per op. Empty rdd: *nonempty = 0 (the reference's None). */
+int vega_gpu_reduce(vega_ctx_t *ctx, vega_rdd_t rdd, vega_op_t op, int64_t *out_k,
+                    void *out_v, int *nonempty);
+/* fold (rdd.rs:311-322): init seeds every partition's fold and the fold
+ * across partitions, so with P = nparts of the handle the result is init
+ * combined P+1 times with reduce(rdd) (SUM: reduce + (P+1)*init). An empty
+ * rdd folds to init combined P+1 times. aggregate(init, seq, comb) collapses
+ * to fold under the fixed op enum. */
+int vega_gpu_fold(vega_ctx_t *ctx, vega_rdd_t rdd, vega_op_t op, int64_t init_k,
+                  const void *init_v, int64_t *out_k, void *out_v);
+/* min / max (rdd.rs:1081-1099): the lexicographic extreme row under Rust's
+ * Ord for (i64, i64). i64-valued rdds only (f64 is not Ord). */
+int vega_gpu_min(vega_ctx_t *ctx, vega_rdd_t rdd, int64_t *out_k, int64_t *out_v,
+                 int *nonempty);
+int vega_gpu_max(vega_ctx_t *ctx, vega_rdd_t rdd, int64_t *out_k, int64_t *out_v,
+                 int *nonempty);
+/* take (rdd.rs:565-620): the first min(num, n) rows in partition order (the
+ * row prefix). keys/vals sized min(num, n). */
+int vega_gpu_take(vega_ctx_t *ctx, vega_rdd_t rdd, uint64_t num, int64_t *keys,
+                  void *vals, uint64_t *n_out);
+/* first (rdd.rs:534-543): take(1); an empty rdd is VEGA_ERR_UNSUPPORTED with
+ * "empty collection" in vega_gpu_last_error */
+int vega_gpu_first(vega_ctx_t *ctx, vega_rdd_t rdd, int64_t *k, void *v);
+/* is_empty (rdd.rs:1073-1078) */
+int vega_gpu_is_empty(vega_ctx_t *ctx, vega_rdd_t rdd, int *empty);
+/* take_ordered (rdd.rs:1124-1153): the min(num, n) lexicographically smallest
+ * rows ascending; top (rdd.rs:1106-1117): the largest, descending. MSB radix
+ * select — no full sort, O(num) extra memory. i64-valued rdds only. */
+int vega_gpu_take_ordered(vega_ctx_t *ctx, vega_rdd_t rdd, uint64_t num, int64_t *keys,
+                          int64_t *vals, uint64_t *n_out);
+int vega_gpu_top(vega_ctx_t *ctx, vega_rdd_t rdd, uint64_t num, int64_t *keys,
+                 int64_t *vals, uint64_t *n_out);
 int vega_gpu_free_rdd(vega_ctx_t *ctx, vega_rdd_t rdd);
 
 /* ---------------- profiling ---------------- */
@@ -257,6 +297,27 @@ int vega_dev_join_grouped(void *stream, const int64_t *ak, const int64_t *av, ui
  * oracle_checksum_pairs_i64) — large-size parity checks without D2H */
 int vega_dev_checksum_pairs(void *stream, const int64_t *keys, const int64_t *vals,
                             uint64_t n, uint64_t *h_sum, void *d_ws, size_t ws_bytes);
+
+/* MSB radix select over the 128-bit composite (flip(k), flip(v)): writes the
+ * min(num, n) lexicographically smallest (descending != 0: largest) rows,
+ * sorted ascending (descending), to the DEVICE buffers out_k/out_v (num
+ * rows). keys/vals are not modified. cand_cap bounds the threshold bucket
+ * that is compacted and sorted (0 = the default, 1 << 20); memory is
+ * O(num + cand_cap), never O(n). *h_passes = histogram passes made (0 when
+ * num >= n or num == 0). d_ws must hold
+ * vega_dev_select_ws_bytes(min(num, n), cand_cap) bytes, else VEGA_ERR_CAP.
+ * Synchronizes the stream before returning. */
+size_t vega_dev_select_ws_bytes(uint64_t num, uint64_t cand_cap);
+int vega_dev_select_k_i64(void *stream, const int64_t *keys, const int64_t *vals, uint64_t n,
+                          uint64_t num, int descending, uint64_t cand_cap,
+                          int64_t *out_k, int64_t *out_v, uint64_t *h_nout, int *h_passes,
+                          void *d_ws, size_t ws_bytes);
+/* column-wise reduce of n >= 1 device rows to one HOST row (the op set of
+ * vega_gpu_reduce; vals / h_out_v are double for SUM_F64). d_ws: 64 KiB
+ * suffices (VEGA_ERR_CAP if too small). */
+int vega_dev_reduce_pairs(void *stream, const int64_t *keys, const void *vals, uint64_t n,
+                          int op, int64_t *h_out_k, void *h_out_v, void *d_ws,
+                          size_t ws_bytes);
 
 #ifdef __cplusplus
 }

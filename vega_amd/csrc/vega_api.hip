@@ -70,8 +70,7 @@ struct vega_ctx {
         }                                                                      \
     } while (0)
 
-static int ensure_ws(vega_ctx *c, uint64_t n) {
-    size_t need = ws_bytes_for(n);
+static int ensure_ws_bytes(vega_ctx *c, size_t need) {
     if (c->ws_bytes >= need) return VEGA_OK;
     if (c->ws) (void)hipFree(c->ws);
     c->ws = nullptr;
@@ -80,6 +79,8 @@ static int ensure_ws(vega_ctx *c, uint64_t n) {
     c->ws_bytes = need;
     return VEGA_OK;
 }
+
+static int ensure_ws(vega_ctx *c, uint64_t n) { return ensure_ws_bytes(c, ws_bytes_for(n)); }
 
 static RddImpl *get_rdd(vega_ctx *c, vega_rdd_t h) {
     auto it = c->rdds.find(h);
@@ -953,6 +954,210 @@ int vega_gpu_collect(vega_ctx_t *c, vega_rdd_t rdd, int64_t *keys, void *vals, u
     return VEGA_OK;
 }
 
+/* ---------------- device-side actions ---------------- */
+/* reduce / fold / min / max / take / first / is_empty / take_ordered / top
+ * (rdd.rs:274-322, :534-620, :1073-1153). Plain pair handles only; the input
+ * is never modified; rows stay in HBM — only the answer crosses to the host. */
+
+/* common guards; *out = the plain pair rdd */
+static int action_rdd(vega_ctx *c, vega_rdd_t rdd, RddImpl **out) {
+    if (!c) return VEGA_ERR_INVALID;
+    if (c->ngpus > 1) return VEGA_ERR_UNSUPPORTED; /* G>1: north-star ops only */
+    RddImpl *r = get_rdd(c, rdd);
+    if (!r || r->grouped || r->d_v2) return VEGA_ERR_INVALID;
+    if (r->n >= (1ULL << 32)) {
+        snprintf(c->err, sizeof c->err, "action on %llu rows exceeds the 2^32-1 per-call limit",
+                 (unsigned long long)r->n);
+        return VEGA_ERR_UNSUPPORTED;
+    }
+    *out = r;
+    return VEGA_OK;
+}
+
+/* device reduction of a non-empty rdd to one row (internal op codes) */
+static int reduce_rows(vega_ctx *c, RddImpl *r, int op, int64_t *out_k, void *out_v) {
+    int rc = ensure_ws_bytes(c, 1 << 16);
+    if (rc) return rc;
+    Ws ws(c->ws, c->ws_bytes);
+    CTX_TRY(c, col_reduce(c->stream, r->d_k, r->d_v, r->n, op, out_k, out_v, ws));
+    return VEGA_OK;
+}
+
+/* the reduce_common type guards: SUM_F64 needs f64 values, the i64 ops need
+ * i64 values, COUNT is not a reduce closure */
+static bool action_op_ok(const RddImpl *r, int op) {
+    if (op == VEGA_OP_SUM_F64) return r->vtype == 1;
+    if (op == VEGA_OP_SUM_I64 || op == VEGA_OP_MIN_I64 || op == VEGA_OP_MAX_I64)
+        return r->vtype == 0;
+    return false;
+}
+
+int vega_gpu_reduce(vega_ctx_t *c, vega_rdd_t rdd, vega_op_t op, int64_t *out_k,
+                    void *out_v, int *nonempty) {
+    RddImpl *r;
+    int rc = action_rdd(c, rdd, &r);
+    if (rc) return rc;
+    if (!out_k || !out_v || !nonempty || !action_op_ok(r, (int)op)) return VEGA_ERR_INVALID;
+    *nonempty = r->n != 0;
+    if (!r->n) return VEGA_OK; /* rdd.rs:289: None */
+    return reduce_rows(c, r, (int)op, out_k, out_v);
+}
+
+/* fold (rdd.rs:311-322): init seeds every partition's fold and the fold
+ * across partitions, so it is combined nparts+1 times — empty partitions
+ * included. One device reduction; the init arithmetic is host-side. */
+int vega_gpu_fold(vega_ctx_t *c, vega_rdd_t rdd, vega_op_t op, int64_t init_k,
+                  const void *init_v, int64_t *out_k, void *out_v) {
+    RddImpl *r;
+    int rc = action_rdd(c, rdd, &r);
+    if (rc) return rc;
+    if (!init_v || !out_k || !out_v || !action_op_ok(r, (int)op)) return VEGA_ERR_INVALID;
+    int64_t rk = 0;
+    uint64_t rv = 0;
+    const bool have = r->n != 0;
+    if (have) {
+        rc = reduce_rows(c, r, (int)op, &rk, &rv);
+        if (rc) return rc;
+    }
+    const uint64_t times = (uint64_t)r->nparts + 1;
+    int64_t iv;
+    memcpy(&iv, init_v, 8);
+    if (op == VEGA_OP_SUM_I64 || op == VEGA_OP_SUM_F64)
+        *out_k = (int64_t)((uint64_t)rk + times * (uint64_t)init_k);
+    else if (op == VEGA_OP_MIN_I64)
+        *out_k = have && rk < init_k ? rk : init_k;
+    else
+        *out_k = have && rk > init_k ? rk : init_k;
+    if (op == VEGA_OP_SUM_I64) {
+        int64_t o = (int64_t)(rv + times * (uint64_t)iv);
+        memcpy(out_v, &o, 8);
+    } else if (op == VEGA_OP_SUM_F64) {
+        double init, acc;
+        memcpy(&init, init_v, 8);
+        memcpy(&acc, &rv, 8);
+        uint64_t left = times;
+        if (!have) { acc = init; left--; }
+        for (uint64_t i = 0; i < left; ++i) acc += init;
+        memcpy(out_v, &acc, 8);
+    } else {
+        int64_t red = (int64_t)rv, o;
+        if (op == VEGA_OP_MIN_I64) o = have && red < iv ? red : iv;
+        else o = have && red > iv ? red : iv;
+        memcpy(out_v, &o, 8);
+    }
+    return VEGA_OK;
+}
+
+static int extreme_common(vega_ctx *c, vega_rdd_t rdd, int op, int64_t *out_k,
+                          int64_t *out_v, int *nonempty) {
+    RddImpl *r;
+    int rc = action_rdd(c, rdd, &r);
+    if (rc) return rc;
+    /* f64 is not Ord in the reference either */
+    if (!out_k || !out_v || !nonempty || r->vtype != 0) return VEGA_ERR_INVALID;
+    *nonempty = r->n != 0;
+    if (!r->n) return VEGA_OK;
+    return reduce_rows(c, r, op, out_k, out_v);
+}
+
+int vega_gpu_min(vega_ctx_t *c, vega_rdd_t rdd, int64_t *out_k, int64_t *out_v, int *nonempty) {
+    return extreme_common(c, rdd, COLRED_LEXMIN, out_k, out_v, nonempty);
+}
+int vega_gpu_max(vega_ctx_t *c, vega_rdd_t rdd, int64_t *out_k, int64_t *out_v, int *nonempty) {
+    return extreme_common(c, rdd, COLRED_LEXMAX, out_k, out_v, nonempty);
+}
+
+/* take (rdd.rs:565-620): partitions are contiguous row slices, so the first
+ * num rows in partition order are the row prefix */
+int vega_gpu_take(vega_ctx_t *c, vega_rdd_t rdd, uint64_t num, int64_t *keys, void *vals,
+                  uint64_t *n_out) {
+    RddImpl *r;
+    int rc = action_rdd(c, rdd, &r);
+    if (rc) return rc;
+    if (!n_out) return VEGA_ERR_INVALID;
+    uint64_t m = num < r->n ? num : r->n;
+    if (m && (!keys || !vals)) return VEGA_ERR_INVALID;
+    *n_out = m;
+    if (m) {
+        CTX_TRY(c, hipMemcpyAsync(keys, r->d_k, m * 8, hipMemcpyDeviceToHost, c->stream));
+        CTX_TRY(c, hipMemcpyAsync(vals, r->d_v, m * 8, hipMemcpyDeviceToHost, c->stream));
+        CTX_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    return VEGA_OK;
+}
+
+int vega_gpu_first(vega_ctx_t *c, vega_rdd_t rdd, int64_t *k, void *v) {
+    RddImpl *r;
+    int rc = action_rdd(c, rdd, &r);
+    if (rc) return rc;
+    if (!r->n) { /* rdd.rs:541 UnsupportedOperation("empty collection") */
+        snprintf(c->err, sizeof c->err, "first: empty collection");
+        return VEGA_ERR_UNSUPPORTED;
+    }
+    uint64_t m = 0;
+    return vega_gpu_take(c, rdd, 1, k, v, &m);
+}
+
+int vega_gpu_is_empty(vega_ctx_t *c, vega_rdd_t rdd, int *empty) {
+    RddImpl *r;
+    int rc = action_rdd(c, rdd, &r);
+    if (rc) return rc;
+    if (!empty) return VEGA_ERR_INVALID;
+    *empty = r->n == 0;
+    return VEGA_OK;
+}
+
+static int ordered_common(vega_ctx *c, vega_rdd_t rdd, uint64_t num, bool descending,
+                          int64_t *keys, int64_t *vals, uint64_t *n_out) {
+    RddImpl *r;
+    int rc = action_rdd(c, rdd, &r);
+    if (rc) return rc;
+    if (!n_out || r->vtype != 0) return VEGA_ERR_INVALID;
+    uint64_t m = num < r->n ? num : r->n;
+    if (m && (!keys || !vals)) return VEGA_ERR_INVALID;
+    *n_out = 0;
+    if (!m) return VEGA_OK;
+    rc = ensure_ws_bytes(c, select_ws_bytes(m, 0));
+    if (rc) return rc;
+    int64_t *ok = nullptr, *ov = nullptr;
+    hipError_t e = hipSuccess;
+    const char *msg = "";
+    int ret = VEGA_ERR_HIP;
+    do {
+        if ((e = hipMalloc(&ok, m * 8)) != hipSuccess) break;
+        if ((e = hipMalloc(&ov, m * 8)) != hipSuccess) break;
+        Ws ws(c->ws, c->ws_bytes);
+        uint64_t nout = 0;
+        int passes = 0;
+        if ((e = select_k(c->stream, r->d_k, (const int64_t *)r->d_v, r->n, m, descending, 0,
+                          ok, ov, &nout, &passes, ws, &msg)) != hipSuccess) break;
+        if ((e = hipMemcpyAsync(keys, ok, m * 8, hipMemcpyDeviceToHost, c->stream)) != hipSuccess) break;
+        if ((e = hipMemcpyAsync(vals, ov, m * 8, hipMemcpyDeviceToHost, c->stream)) != hipSuccess) break;
+        if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) break;
+        *n_out = nout;
+        ret = VEGA_OK;
+    } while (0);
+    if (e != hipSuccess) {
+        snprintf(c->err, sizeof c->err, "%s: %s%s%s", descending ? "top" : "take_ordered",
+                 hipGetErrorString(e), *msg ? " — " : "", msg);
+        if (e == hipErrorNotSupported) ret = VEGA_ERR_UNSUPPORTED;
+        if (e == hipErrorOutOfMemory) ret = VEGA_ERR_NOMEM;
+    }
+    (void)hipStreamSynchronize(c->stream);
+    if (ok) (void)hipFree(ok);
+    if (ov) (void)hipFree(ov);
+    return ret;
+}
+
+int vega_gpu_take_ordered(vega_ctx_t *c, vega_rdd_t rdd, uint64_t num, int64_t *keys,
+                          int64_t *vals, uint64_t *n_out) {
+    return ordered_common(c, rdd, num, false, keys, vals, n_out);
+}
+int vega_gpu_top(vega_ctx_t *c, vega_rdd_t rdd, uint64_t num, int64_t *keys, int64_t *vals,
+                 uint64_t *n_out) {
+    return ordered_common(c, rdd, num, true, keys, vals, n_out);
+}
+
 int vega_gpu_free_rdd(vega_ctx_t *c, vega_rdd_t rdd) {
     auto it = c->rdds.find(rdd);
     if (it == c->rdds.end()) return VEGA_ERR_INVALID;
@@ -1074,6 +1279,50 @@ int vega_dev_join_grouped(void *stream, const int64_t *ak, const int64_t *av, ui
     hipError_t e = join_sorted((hipStream_t)stream, ak, av, na, bk, bv, nb, order_mode,
                                out_k, out_va, out_vb, cap, h_nout, ws);
     return e == hipSuccess ? VEGA_OK : VEGA_ERR_HIP;
+}
+
+size_t vega_dev_select_ws_bytes(uint64_t num, uint64_t cand_cap) {
+    return select_ws_bytes(num, cand_cap);
+}
+
+/* MSB radix select (top / take_ordered on device buffers). The workspace is
+ * checked against vega_dev_select_ws_bytes(min(num, n), cand_cap) before
+ * anything is launched. */
+int vega_dev_select_k_i64(void *stream, const int64_t *keys, const int64_t *vals, uint64_t n,
+                          uint64_t num, int descending, uint64_t cand_cap,
+                          int64_t *out_k, int64_t *out_v, uint64_t *h_nout, int *h_passes,
+                          void *d_ws, size_t ws_bytes) {
+    if (!h_nout || !h_passes) return VEGA_ERR_INVALID;
+    *h_nout = 0;
+    *h_passes = 0;
+    if (n >= (1ULL << 32)) return VEGA_ERR_UNSUPPORTED;
+    const uint64_t m = num < n ? num : n;
+    if (!m) return VEGA_OK;
+    if (!keys || !vals || !out_k || !out_v) return VEGA_ERR_INVALID;
+    if (!d_ws || ws_bytes < select_ws_bytes(m, cand_cap)) return VEGA_ERR_CAP;
+    Ws ws(d_ws, ws_bytes);
+    const char *msg = "";
+    hipError_t e = select_k((hipStream_t)stream, keys, vals, n, m, descending != 0, cand_cap,
+                            out_k, out_v, h_nout, h_passes, ws, &msg);
+    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+    if (e != hipSuccess && *msg) fprintf(stderr, "vega_dev_select_k_i64: %s\n", msg);
+    if (e == hipErrorNotSupported) return VEGA_ERR_UNSUPPORTED;
+    return e == hipSuccess ? VEGA_OK : (e == hipErrorOutOfMemory ? VEGA_ERR_CAP : VEGA_ERR_HIP);
+}
+
+/* column-wise reduce of device rows to one host row (op: the four reduce
+ * ops of vega_gpu_reduce; vals/h_out_v are double for SUM_F64). n == 0 is
+ * VEGA_ERR_INVALID: there is no row to return. */
+int vega_dev_reduce_pairs(void *stream, const int64_t *keys, const void *vals, uint64_t n, int op,
+                          int64_t *h_out_k, void *h_out_v, void *d_ws, size_t ws_bytes) {
+    if (!n || !keys || !vals || !h_out_k || !h_out_v) return VEGA_ERR_INVALID;
+    if (op != VEGA_OP_SUM_I64 && op != VEGA_OP_SUM_F64 && op != VEGA_OP_MIN_I64 &&
+        op != VEGA_OP_MAX_I64)
+        return VEGA_ERR_INVALID;
+    Ws ws(d_ws, ws_bytes);
+    hipError_t e = col_reduce((hipStream_t)stream, keys, vals, n, op, h_out_k, h_out_v, ws);
+    if (e == hipErrorNotSupported) return VEGA_ERR_UNSUPPORTED;
+    return e == hipSuccess ? VEGA_OK : (e == hipErrorOutOfMemory ? VEGA_ERR_CAP : VEGA_ERR_HIP);
 }
 
 /* diagnostic (VEGA_PHASE_PROF=1 builds/runs): per-phase shader-cycle sums of

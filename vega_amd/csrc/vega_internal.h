@@ -133,6 +133,34 @@ hipError_t cogroup_index(hipStream_t s, const int64_t *ka_u, uint64_t nka,
                          uint64_t *o_offa, uint64_t *o_lena, uint64_t *o_offb,
                          uint64_t *o_lenb, uint64_t cap, uint64_t *h_nk, Ws &ws);
 
+/* ---- device-side actions (rdd.rs reduce/fold/min/max/top/take_ordered) ---- */
+
+/* col_reduce ops: the vega_op_t values 0/2/3/4 applied COLUMN-WISE (key
+ * column always i64), plus the lexicographic extreme row under (i64, i64) */
+enum { COLRED_LEXMIN = 100, COLRED_LEXMAX = 101 };
+
+/* one-pass reduction of n >= 1 rows to a single (k, v) row on the host (after
+ * an internal stream sync). No atomics: per-block partials are folded in
+ * block-index order by a second one-block kernel, so the f64 sum is
+ * bit-stable for a given n. */
+hipError_t col_reduce(hipStream_t s, const int64_t *keys, const void *vals, uint64_t n,
+                      int op, int64_t *h_out_k, void *h_out_v, Ws &ws);
+
+/* candidate-bucket bound of select_k when the caller passes 0 */
+constexpr uint64_t SELECT_CAND_CAP_DEFAULT = 1ULL << 20;
+
+/* workspace for select_k: O(num + cand_cap), nothing proportional to n */
+size_t select_ws_bytes(uint64_t num, uint64_t cand_cap);
+
+/* MSB radix select over the 128-bit composite (flip(k), flip(v)): the
+ * min(num, n) lexicographically smallest (descending: largest) rows, sorted
+ * ascending (descending), into out_k/out_v (device, num rows). *h_passes =
+ * number of histogram passes. On failure *err (if non-null) names the cause. */
+hipError_t select_k(hipStream_t s, const int64_t *keys, const int64_t *vals, uint64_t n,
+                    uint64_t num, bool descending, uint64_t cand_cap,
+                    int64_t *out_k, int64_t *out_v, uint64_t *h_nout, int *h_passes,
+                    Ws &ws, const char **err);
+
 size_t ws_bytes_for(uint64_t n);
 
 /* diagnostic phase-cycle buffer (VEGA_PHASE_PROF=1|2), else nullptr */

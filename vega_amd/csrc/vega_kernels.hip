@@ -2365,4 +2365,507 @@ hipError_t join_sorted(hipStream_t s, const int64_t *ak, const int64_t *av, uint
     return hipSuccess;
 }
 
+/* ------------------------------------------------------------------ */
+/* device-side actions: column reduce (rdd.rs:274-322 reduce/fold,
+ * :1081-1099 min/max) and MSB radix select (rdd.rs:1106-1153 top /
+ * take_ordered). Both are single streaming reads of the columns with a
+ * fixed grid (<= 2048 blocks) and a block-uniform grid-stride loop; no
+ * inter-block waiting of any kind. */
+
+constexpr int ACT_U = 4; /* 2-row units per thread per sweep (loads in flight) */
+
+static inline uint32_t act_grid(uint64_t n) {
+    uint64_t units = (n + 1) >> 1;
+    uint64_t g = (units + (uint64_t)BLOCK * ACT_U - 1) / ((uint64_t)BLOCK * ACT_U);
+    return (uint32_t)(g < 1 ? 1 : (g > 2048 ? 2048 : g));
+}
+
+/* rows 2u and 2u+1 of one column: a single 16-B load when the pair is whole
+ * (VEC: column 16-B aligned), never reading past row n-1 */
+template <bool VEC>
+__device__ __forceinline__ void load_pair(const uint64_t *col, uint64_t u, uint64_t n,
+                                          uint64_t &a, uint64_t &b) {
+    const uint64_t r = 2 * u;
+    a = 0;
+    b = 0;
+    if (VEC) {
+        if (r + 1 < n) {
+            ulonglong2 t = ((const ulonglong2 *)col)[u];
+            a = t.x;
+            b = t.y;
+        } else if (r < n) {
+            a = col[r];
+        }
+    } else {
+        if (r < n) a = col[r];
+        if (r + 1 < n) b = col[r + 1];
+    }
+}
+
+/* OP: 0 SUM_I64, 2 SUM_F64, 3 MIN_I64, 4 MAX_I64 (column-wise; key column
+ * always wrapping/ordered i64), COLRED_LEXMIN / COLRED_LEXMAX (row-wise) */
+template <int OP>
+__device__ __forceinline__ void cr_identity(uint64_t &k, uint64_t &v) {
+    if (OP == 0) { k = 0; v = 0; }
+    else if (OP == 2) { k = 0; v = 0x8000000000000000ULL; /* -0.0: x + -0.0 == x */ }
+    else if (OP == 3 || OP == COLRED_LEXMIN) { k = (uint64_t)INT64_MAX; v = (uint64_t)INT64_MAX; }
+    else { k = (uint64_t)INT64_MIN; v = (uint64_t)INT64_MIN; }
+}
+template <int OP>
+__device__ __forceinline__ void cr_combine(uint64_t &k, uint64_t &v, uint64_t k2, uint64_t v2) {
+    if (OP == 0) {
+        k += k2;
+        v += v2;
+    } else if (OP == 2) {
+        k += k2;
+        v = (uint64_t)__double_as_longlong(__longlong_as_double((long long)v) +
+                                           __longlong_as_double((long long)v2));
+    } else if (OP == 3) {
+        if ((int64_t)k2 < (int64_t)k) k = k2;
+        if ((int64_t)v2 < (int64_t)v) v = v2;
+    } else if (OP == 4) {
+        if ((int64_t)k2 > (int64_t)k) k = k2;
+        if ((int64_t)v2 > (int64_t)v) v = v2;
+    } else if (OP == COLRED_LEXMIN) {
+        if ((int64_t)k2 < (int64_t)k || (k2 == k && (int64_t)v2 < (int64_t)v)) { k = k2; v = v2; }
+    } else {
+        if ((int64_t)k2 > (int64_t)k || (k2 == k && (int64_t)v2 > (int64_t)v)) { k = k2; v = v2; }
+    }
+}
+
+/* wave (shuffle) then block (LDS, waves folded in order) reduction; the
+ * block result is valid in thread 0 */
+template <int OP>
+__device__ __forceinline__ void cr_block_reduce(uint64_t &ak, uint64_t &av,
+                                                uint64_t *sk, uint64_t *sv) {
+    for (int off = 32; off > 0; off >>= 1) {
+        uint64_t k2 = (uint64_t)__shfl_down((unsigned long long)ak, off);
+        uint64_t v2 = (uint64_t)__shfl_down((unsigned long long)av, off);
+        cr_combine<OP>(ak, av, k2, v2);
+    }
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if (lane == 0) { sk[w] = ak; sv[w] = av; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        ak = sk[0];
+        av = sv[0];
+        for (int i = 1; i < BLOCK / 64; ++i) cr_combine<OP>(ak, av, sk[i], sv[i]);
+    }
+}
+
+template <int OP, bool VEC>
+__global__ __launch_bounds__(BLOCK) void k_col_reduce(const uint64_t *keys, const uint64_t *vals,
+                                                      uint64_t n, uint64_t *pk, uint64_t *pv) {
+    __shared__ uint64_t sk[BLOCK / 64], sv[BLOCK / 64];
+    uint64_t ak, av;
+    cr_identity<OP>(ak, av);
+    const uint64_t units = (n + 1) >> 1;
+    const uint64_t sweep = (uint64_t)gridDim.x * (BLOCK * ACT_U);
+    for (uint64_t b0 = (uint64_t)blockIdx.x * (BLOCK * ACT_U); b0 < units; b0 += sweep) {
+        uint64_t k0[ACT_U], k1[ACT_U], v0[ACT_U], v1[ACT_U];
+#pragma unroll
+        for (int j = 0; j < ACT_U; ++j) {
+            uint64_t u = b0 + (uint64_t)j * BLOCK + threadIdx.x;
+            load_pair<VEC>(keys, u, n, k0[j], k1[j]);
+            load_pair<VEC>(vals, u, n, v0[j], v1[j]);
+        }
+#pragma unroll
+        for (int j = 0; j < ACT_U; ++j) {
+            uint64_t r = 2 * (b0 + (uint64_t)j * BLOCK + threadIdx.x);
+            if (r < n) cr_combine<OP>(ak, av, k0[j], v0[j]);
+            if (r + 1 < n) cr_combine<OP>(ak, av, k1[j], v1[j]);
+        }
+    }
+    cr_block_reduce<OP>(ak, av, sk, sv);
+    if (threadIdx.x == 0) {
+        pk[blockIdx.x] = ak;
+        pv[blockIdx.x] = av;
+    }
+}
+
+/* one block folds the np per-block partials in block-index order: thread t
+ * owns the contiguous slice [t*c, (t+1)*c), then the same wave/block fold */
+template <int OP>
+__global__ __launch_bounds__(BLOCK) void k_col_reduce_final(const uint64_t *pk, const uint64_t *pv,
+                                                            uint32_t np, uint64_t *out) {
+    __shared__ uint64_t sk[BLOCK / 64], sv[BLOCK / 64];
+    uint64_t ak, av;
+    cr_identity<OP>(ak, av);
+    const uint32_t c = (np + BLOCK - 1) / BLOCK;
+    const uint32_t lo = threadIdx.x * c;
+    const uint32_t hi = lo + c < np ? lo + c : np;
+    for (uint32_t i = lo; i < hi; ++i) cr_combine<OP>(ak, av, pk[i], pv[i]);
+    cr_block_reduce<OP>(ak, av, sk, sv);
+    if (threadIdx.x == 0) {
+        out[0] = ak;
+        out[1] = av;
+    }
+}
+
+template <int OP>
+static hipError_t col_reduce_launch(hipStream_t s, const uint64_t *k, const uint64_t *v,
+                                    uint64_t n, uint32_t grid, bool vec, uint64_t *pk,
+                                    uint64_t *pv, uint64_t *out) {
+    if (vec)
+        hipLaunchKernelGGL((k_col_reduce<OP, true>), dim3(grid), dim3(BLOCK), 0, s, k, v, n, pk, pv);
+    else
+        hipLaunchKernelGGL((k_col_reduce<OP, false>), dim3(grid), dim3(BLOCK), 0, s, k, v, n, pk, pv);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL((k_col_reduce_final<OP>), dim3(1), dim3(BLOCK), 0, s,
+                       (const uint64_t *)pk, (const uint64_t *)pv, grid, out);
+    return hipGetLastError();
+}
+
+hipError_t col_reduce(hipStream_t s, const int64_t *keys, const void *vals, uint64_t n,
+                      int op, int64_t *h_out_k, void *h_out_v, Ws &ws) {
+    if (n == 0) return hipErrorInvalidValue; /* callers answer the empty case */
+    if (n >= (1ULL << 32)) return hipErrorNotSupported;
+    const uint32_t grid = act_grid(n); /* pure function of n: fixed f64 sum shape */
+    uint64_t *pk = (uint64_t *)ws.take(2048 * 8);
+    uint64_t *pv = (uint64_t *)ws.take(2048 * 8);
+    uint64_t *out = (uint64_t *)ws.take(16);
+    if (!pk || !pv || !out) return hipErrorOutOfMemory;
+    const bool vec = ((((uintptr_t)keys) | ((uintptr_t)vals)) & 15) == 0;
+    const uint64_t *k = (const uint64_t *)keys, *v = (const uint64_t *)vals;
+    {
+        ProfScope ps("col_reduce", s);
+        switch (op) {
+        case 0: HIP_TRY((col_reduce_launch<0>(s, k, v, n, grid, vec, pk, pv, out))); break;
+        case 2: HIP_TRY((col_reduce_launch<2>(s, k, v, n, grid, vec, pk, pv, out))); break;
+        case 3: HIP_TRY((col_reduce_launch<3>(s, k, v, n, grid, vec, pk, pv, out))); break;
+        case 4: HIP_TRY((col_reduce_launch<4>(s, k, v, n, grid, vec, pk, pv, out))); break;
+        case COLRED_LEXMIN:
+            HIP_TRY((col_reduce_launch<COLRED_LEXMIN>(s, k, v, n, grid, vec, pk, pv, out))); break;
+        case COLRED_LEXMAX:
+            HIP_TRY((col_reduce_launch<COLRED_LEXMAX>(s, k, v, n, grid, vec, pk, pv, out))); break;
+        default: return hipErrorInvalidValue;
+        }
+    }
+    uint64_t h[2];
+    HIP_TRY(hipMemcpyAsync(h, out, 16, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    *h_out_k = (int64_t)h[0];
+    memcpy(h_out_v, &h[1], 8);
+    return hipSuccess;
+}
+
+/* ---- MSB radix select ---- */
+
+/* select state: the composite of a row is (k ^ x, v ^ x) with x = sign-bit
+ * flip (ascending) or its complement (descending: the same ascending select
+ * then finds the largest rows). p_* = prefix digits consumed so far (low
+ * bits zero), m_* = mask of the consumed bits, ndig = digits consumed. */
+struct SelState {
+    uint64_t p_hi, p_lo, m_hi, m_lo, x;
+    int ndig;
+};
+
+/* wave-private histogram add; a wave whose matching lanes all carry one
+ * digit (narrow keys: constant high bytes) costs one LDS atomic, not 64
+ * same-address ones. Must be reached by the whole wave. */
+__device__ __forceinline__ void sel_hist_add(uint32_t *h, uint32_t d, bool match) {
+    const uint64_t m = __ballot(match);
+    if (m == 0) return;
+    const int lead = __ffsll((unsigned long long)m) - 1;
+    const uint32_t d0 = (uint32_t)__shfl((int)d, lead);
+    const uint64_t same = __ballot(match && d == d0);
+    if (same == m) {
+        if ((int)(threadIdx.x & 63) == lead) atomicAdd(&h[d0], (uint32_t)__popcll(m));
+    } else if (match) {
+        atomicAdd(&h[d], 1u);
+    }
+}
+
+/* 256-bin histogram of digit st.ndig over rows matching the prefix. VALD:
+ * the digit lies in the value column (both columns read, 16 B/row); else
+ * only the key column is read (8 B/row). */
+template <bool VALD, bool VEC>
+__global__ __launch_bounds__(BLOCK) void k_select_hist(const uint64_t *keys, const uint64_t *vals,
+                                                       uint64_t n, SelState st, uint32_t *ghist) {
+    __shared__ uint32_t sh[BLOCK / 64][256];
+    for (int i = threadIdx.x; i < (BLOCK / 64) * 256; i += BLOCK) ((uint32_t *)sh)[i] = 0;
+    __syncthreads();
+    uint32_t *myh = sh[threadIdx.x >> 6];
+    const int shift = 56 - 8 * (st.ndig & 7);
+    const uint64_t units = (n + 1) >> 1;
+    const uint64_t sweep = (uint64_t)gridDim.x * (BLOCK * ACT_U);
+    for (uint64_t b0 = (uint64_t)blockIdx.x * (BLOCK * ACT_U); b0 < units; b0 += sweep) {
+        uint64_t kk[ACT_U][2], vv[ACT_U][2];
+#pragma unroll
+        for (int j = 0; j < ACT_U; ++j) {
+            uint64_t u = b0 + (uint64_t)j * BLOCK + threadIdx.x;
+            load_pair<VEC>(keys, u, n, kk[j][0], kk[j][1]);
+            if (VALD) load_pair<VEC>(vals, u, n, vv[j][0], vv[j][1]);
+        }
+#pragma unroll
+        for (int j = 0; j < ACT_U; ++j) {
+            uint64_t r = 2 * (b0 + (uint64_t)j * BLOCK + threadIdx.x);
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                const uint64_t hi = kk[j][e] ^ st.x;
+                bool match = (r + e < n) && (((hi ^ st.p_hi) & st.m_hi) == 0);
+                uint64_t src = hi;
+                if (VALD) {
+                    const uint64_t lo = vv[j][e] ^ st.x;
+                    match = match && (((lo ^ st.p_lo) & st.m_lo) == 0);
+                    src = lo;
+                }
+                sel_hist_add(myh, (uint32_t)(src >> shift) & 0xFFu, match);
+            }
+        }
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < 256; i += BLOCK) {
+        uint32_t c = 0;
+        for (int w = 0; w < BLOCK / 64; ++w) c += sh[w][i];
+        if (c) atomicAdd(&ghist[i], c);
+    }
+}
+
+/* append every row strictly below the prefix, and (take_bucket) every row
+ * matching it, to the candidate buffer. Aggregated append: per-slot wave
+ * ballots + popcounts give every taken row its offset, the four wave totals
+ * meet in LDS and ONE returning atomicAdd per block per sweep reserves the
+ * range (all appends share one counter, so the atomic count bounds the pass
+ * once the bucket nears cand_cap). A sweep with no taken row costs one
+ * barrier and no atomic. VALD: value digits were
+ * consumed (compare both columns); else the compare is key-only and the
+ * value is fetched for taken rows only. Every write is checked against cap;
+ * overflow sets ctl[1]. */
+template <bool VALD, bool VEC>
+__global__ __launch_bounds__(BLOCK) void k_select_compact(const uint64_t *keys, const uint64_t *vals,
+                                                          uint64_t n, SelState st, int take_bucket,
+                                                          uint64_t *ck, uint64_t *cv, uint64_t cap,
+                                                          uint32_t *ctl) {
+    /* wave totals are double-buffered by sweep parity: a wave that skips an
+     * empty sweep may publish its next total while a slower wave still reads */
+    __shared__ uint32_t wtot[2][BLOCK / 64];
+    __shared__ uint32_t sbase;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const uint64_t lt = (1ULL << lane) - 1;
+    const uint64_t units = (n + 1) >> 1;
+    const uint64_t sweep = (uint64_t)gridDim.x * (BLOCK * ACT_U);
+    int par = 0;
+    for (uint64_t b0 = (uint64_t)blockIdx.x * (BLOCK * ACT_U); b0 < units; b0 += sweep, par ^= 1) {
+        uint64_t kk[ACT_U][2], vv[ACT_U][2];
+#pragma unroll
+        for (int j = 0; j < ACT_U; ++j) {
+            uint64_t u = b0 + (uint64_t)j * BLOCK + threadIdx.x;
+            load_pair<VEC>(keys, u, n, kk[j][0], kk[j][1]);
+            if (VALD) load_pair<VEC>(vals, u, n, vv[j][0], vv[j][1]);
+        }
+        uint64_t ms[ACT_U][2]; /* wave-uniform take masks, one per row slot */
+        uint32_t wcnt = 0;
+#pragma unroll
+        for (int j = 0; j < ACT_U; ++j) {
+            uint64_t r = 2 * (b0 + (uint64_t)j * BLOCK + threadIdx.x);
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                const uint64_t mh = (kk[j][e] ^ st.x) & st.m_hi;
+                bool below = mh < st.p_hi, eq = mh == st.p_hi;
+                if (VALD) {
+                    const uint64_t ml = (vv[j][e] ^ st.x) & st.m_lo;
+                    below = below || (eq && ml < st.p_lo);
+                    eq = eq && ml == st.p_lo;
+                }
+                const bool take = (r + e < n) && (below || (eq && take_bucket));
+                ms[j][e] = __ballot(take);
+                wcnt += (uint32_t)__popcll(ms[j][e]);
+            }
+        }
+        if (lane == 0) wtot[par][w] = wcnt;
+        __syncthreads();
+        uint32_t before = 0, total = 0;
+#pragma unroll
+        for (int i = 0; i < BLOCK / 64; ++i) {
+            uint32_t c = wtot[par][i];
+            if (i < w) before += c;
+            total += c;
+        }
+        if (total == 0) continue; /* block-uniform */
+        if (threadIdx.x == 0) sbase = atomicAdd(&ctl[0], total);
+        __syncthreads();
+        uint64_t pos0 = (uint64_t)sbase + before;
+#pragma unroll
+        for (int j = 0; j < ACT_U; ++j) {
+            uint64_t r = 2 * (b0 + (uint64_t)j * BLOCK + threadIdx.x);
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                const uint64_t m = ms[j][e];
+                if ((m >> lane) & 1) {
+                    const uint64_t pos = pos0 + (uint64_t)__popcll(m & lt);
+                    if (pos < cap) {
+                        ck[pos] = kk[j][e];
+                        cv[pos] = VALD ? vv[j][e] : vals[r + e];
+                    } else {
+                        ctl[1] = 1;
+                    }
+                }
+                pos0 += (uint64_t)__popcll(m);
+            }
+        }
+    }
+}
+
+/* result rows: the first num of the sorted candidates (descending: the last
+ * num, reversed); rows past the m candidates are copies of the threshold row */
+__global__ void k_select_gather(const uint64_t *sk, const uint64_t *sv, uint64_t m, uint64_t num,
+                                int desc, uint64_t tk, uint64_t tv, int64_t *out_k, int64_t *out_v) {
+    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < num; i += stride) {
+        if (i < m) {
+            uint64_t j = desc ? m - 1 - i : i;
+            out_k[i] = (int64_t)sk[j];
+            out_v[i] = (int64_t)sv[j];
+        } else {
+            out_k[i] = (int64_t)tk;
+            out_v[i] = (int64_t)tv;
+        }
+    }
+}
+
+size_t select_ws_bytes(uint64_t num, uint64_t cand_cap) {
+    const uint64_t lim = (1ULL << 32) - 1; /* per-call row limit bounds both */
+    if (!cand_cap) cand_cap = SELECT_CAND_CAP_DEFAULT;
+    if (num > lim) num = lim;
+    if (cand_cap > lim) cand_cap = lim;
+    const uint64_t cap = num + cand_cap;
+    size_t b = 1024 + 256;                      /* digit counters + append ctl */
+    b += 2 * ((cap * 8 + 255) & ~(size_t)255);  /* candidate k, v */
+    b += ws_bytes_for(cap);                     /* candidate sort */
+    return b;
+}
+
+hipError_t select_k(hipStream_t s, const int64_t *keys, const int64_t *vals, uint64_t n,
+                    uint64_t num, bool descending, uint64_t cand_cap,
+                    int64_t *out_k, int64_t *out_v, uint64_t *h_nout, int *h_passes,
+                    Ws &ws, const char **err) {
+    const char *dummy;
+    if (!err) err = &dummy;
+    *err = "";
+    *h_nout = 0;
+    *h_passes = 0;
+    if (n >= (1ULL << 32)) return hipErrorNotSupported;
+    if (num > n) num = n;
+    if (num == 0) return hipSuccess;
+    if (!cand_cap) cand_cap = SELECT_CAND_CAP_DEFAULT;
+    if (cand_cap > (1ULL << 32) - 1) cand_cap = (1ULL << 32) - 1;
+    const uint64_t cap = num + cand_cap;
+    uint32_t *hist = (uint32_t *)ws.take(1024);
+    uint32_t *ctl = (uint32_t *)ws.take(256);
+    uint64_t *ck = (uint64_t *)ws.take(cap * 8);
+    uint64_t *cv = (uint64_t *)ws.take(cap * 8);
+    if (!hist || !ctl || !ck || !cv) return hipErrorOutOfMemory;
+    const uint64_t *k = (const uint64_t *)keys, *v = (const uint64_t *)vals;
+    const bool vec = ((((uintptr_t)keys) | ((uintptr_t)vals)) & 15) == 0;
+    const uint32_t grid = act_grid(n);
+
+    SelState st;
+    st.p_hi = st.p_lo = st.m_hi = st.m_lo = 0;
+    st.x = 0x8000000000000000ULL ^ (descending ? ~0ULL : 0ULL);
+    st.ndig = 0;
+    uint64_t m = 0;      /* candidate rows */
+    bool full = false;   /* all 16 digits consumed with the bucket still > cand_cap */
+    if (num == n) {      /* everything is wanted: sort all rows */
+        HIP_TRY(hipMemcpyAsync(ck, k, n * 8, hipMemcpyDeviceToDevice, s));
+        HIP_TRY(hipMemcpyAsync(cv, v, n * 8, hipMemcpyDeviceToDevice, s));
+        m = n;
+    } else {
+        uint64_t n_below = 0; /* rows strictly below the prefix; invariant < num */
+        uint64_t bucket = 0;
+        for (;;) {
+            HIP_TRY(hipMemsetAsync(hist, 0, 1024, s));
+            {
+                ProfScope ps("select_hist", s);
+                if (st.ndig < 8) {
+                    if (vec) hipLaunchKernelGGL((k_select_hist<false, true>), dim3(grid), dim3(BLOCK), 0, s, k, v, n, st, hist);
+                    else hipLaunchKernelGGL((k_select_hist<false, false>), dim3(grid), dim3(BLOCK), 0, s, k, v, n, st, hist);
+                } else {
+                    if (vec) hipLaunchKernelGGL((k_select_hist<true, true>), dim3(grid), dim3(BLOCK), 0, s, k, v, n, st, hist);
+                    else hipLaunchKernelGGL((k_select_hist<true, false>), dim3(grid), dim3(BLOCK), 0, s, k, v, n, st, hist);
+                }
+                HIP_TRY(hipGetLastError());
+            }
+            uint32_t hc[256];
+            HIP_TRY(hipMemcpyAsync(hc, hist, sizeof hc, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            ++*h_passes;
+            /* threshold bucket d: n_below + sum_{j<d} < num <= n_below + sum_{j<=d} */
+            uint64_t cum = n_below;
+            int d = 0;
+            for (; d < 256; ++d) {
+                if (cum + hc[d] >= num) break;
+                cum += hc[d];
+            }
+            if (d == 256) {
+                *err = "select_k: digit counts do not cover num (inconsistent histogram)";
+                return hipErrorUnknown;
+            }
+            n_below = cum;
+            bucket = hc[d];
+            if (st.ndig < 8) st.p_hi |= (uint64_t)d << (56 - 8 * st.ndig);
+            else st.p_lo |= (uint64_t)d << (56 - 8 * (st.ndig - 8));
+            st.ndig++;
+            st.m_hi = st.ndig >= 8 ? ~0ULL : ~0ULL << (64 - 8 * st.ndig);
+            st.m_lo = st.ndig <= 8 ? 0 : (st.ndig == 16 ? ~0ULL : ~0ULL << (64 - 8 * (st.ndig - 8)));
+            if (bucket <= cand_cap || st.ndig == 16) break;
+        }
+        /* 16 digits consumed: every row of the bucket IS the prefix row, so
+         * the bucket is not compacted — the result is padded with copies */
+        full = bucket > cand_cap;
+        m = n_below + (full ? 0 : bucket);
+        HIP_TRY(hipMemsetAsync(ctl, 0, 8, s));
+        {
+            ProfScope ps("select_compact", s);
+            const int tb = full ? 0 : 1;
+            if (st.ndig > 8) {
+                if (vec) hipLaunchKernelGGL((k_select_compact<true, true>), dim3(grid), dim3(BLOCK), 0, s, k, v, n, st, tb, ck, cv, cap, ctl);
+                else hipLaunchKernelGGL((k_select_compact<true, false>), dim3(grid), dim3(BLOCK), 0, s, k, v, n, st, tb, ck, cv, cap, ctl);
+            } else {
+                if (vec) hipLaunchKernelGGL((k_select_compact<false, true>), dim3(grid), dim3(BLOCK), 0, s, k, v, n, st, tb, ck, cv, cap, ctl);
+                else hipLaunchKernelGGL((k_select_compact<false, false>), dim3(grid), dim3(BLOCK), 0, s, k, v, n, st, tb, ck, cv, cap, ctl);
+            }
+            HIP_TRY(hipGetLastError());
+        }
+        uint32_t hctl[2];
+        HIP_TRY(hipMemcpyAsync(hctl, ctl, 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (hctl[1]) {
+            *err = "select_k: candidate buffer overflow (rows dropped, nothing written out of bounds)";
+            return hipErrorUnknown;
+        }
+        if (hctl[0] != m) {
+            *err = "select_k: compacted row count disagrees with the histograms";
+            return hipErrorUnknown;
+        }
+    }
+
+    /* lexicographic candidate sort: stable by value, then stable by key */
+    const uint64_t *sk = ck, *sv = cv;
+    if (m > 1) {
+        const uint64_t *rk, *rv;
+        {
+            Ws w1 = ws;
+            HIP_TRY(radix_sort_u64(s, cv, ck, m, true, true, w1, &rk, &rv));
+        }
+        if (rk != cv) { /* sorted (v, k) back into the candidate buffers */
+            HIP_TRY(hipMemcpyAsync(cv, rk, m * 8, hipMemcpyDeviceToDevice, s));
+            HIP_TRY(hipMemcpyAsync(ck, rv, m * 8, hipMemcpyDeviceToDevice, s));
+        }
+        {
+            Ws w2 = ws;
+            HIP_TRY(radix_sort_u64(s, ck, cv, m, true, true, w2, &sk, &sv));
+        }
+    }
+    {
+        uint64_t gb = (num + BLOCK - 1) / BLOCK;
+        if (gb > 2048) gb = 2048;
+        hipLaunchKernelGGL(k_select_gather, dim3((uint32_t)gb), dim3(BLOCK), 0, s, sk, sv, m, num,
+                           descending ? 1 : 0, st.p_hi ^ st.x, st.p_lo ^ st.x, out_k, out_v);
+        HIP_TRY(hipGetLastError());
+    }
+    *h_nout = num;
+    return hipSuccess;
+}
+
 } // namespace vega

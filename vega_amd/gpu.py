@@ -298,6 +298,97 @@ class Rdd:
                "collect", self.ctx._c)
         return k[:n.value], v[:n.value]
 
+    # --- device-side actions (rdd.rs:274-322, :534-620, :1073-1153) ---
+    def _vbox(self, op=None):
+        f64 = (op == OP_SUM_F64) if op is not None else self.vdtype == np.float64
+        return ctypes.c_double() if f64 else ctypes.c_int64()
+
+    def reduce(self, op=OP_SUM_I64):
+        """column-wise reduce -> (k, v), or None on an empty rdd"""
+        k = ctypes.c_int64()
+        v = self._vbox(op)
+        ne = ctypes.c_int(0)
+        _check(lib().vega_gpu_reduce(self.ctx._c, ctypes.c_uint64(self.h),
+                                     ctypes.c_int(op), ctypes.byref(k),
+                                     ctypes.byref(v), ctypes.byref(ne)),
+               "reduce", self.ctx._c)
+        return (k.value, v.value) if ne.value else None
+
+    def fold(self, op, init_k, init_v):
+        """fold (rdd.rs:311-322): init combined nparts+1 times with reduce"""
+        k = ctypes.c_int64()
+        v = self._vbox(op)
+        iv = ctypes.c_double(init_v) if op == OP_SUM_F64 else ctypes.c_int64(init_v)
+        _check(lib().vega_gpu_fold(self.ctx._c, ctypes.c_uint64(self.h),
+                                   ctypes.c_int(op), ctypes.c_int64(init_k),
+                                   ctypes.byref(iv), ctypes.byref(k), ctypes.byref(v)),
+               "fold", self.ctx._c)
+        return k.value, v.value
+
+    def _extreme(self, fn, what):
+        k = ctypes.c_int64()
+        v = ctypes.c_int64()
+        ne = ctypes.c_int(0)
+        _check(fn(self.ctx._c, ctypes.c_uint64(self.h), ctypes.byref(k),
+                  ctypes.byref(v), ctypes.byref(ne)), what, self.ctx._c)
+        return (k.value, v.value) if ne.value else None
+
+    def min(self):
+        """lexicographic smallest row, or None on an empty rdd"""
+        return self._extreme(lib().vega_gpu_min, "min")
+
+    def max(self):
+        return self._extreme(lib().vega_gpu_max, "max")
+
+    def _out_rows(self, num):
+        # the entries write min(num, n) rows: a small num sizes the buffers
+        # itself, only a large one is worth a count() call to trim it
+        num = int(num)
+        return num if num <= (1 << 16) else min(num, self.count())
+
+    def take(self, num):
+        """first min(num, n) rows in partition order -> (keys, vals)"""
+        m = self._out_rows(num)
+        k = np.empty(m, dtype=np.int64)
+        v = np.empty(m, dtype=self.vdtype)
+        n = ctypes.c_uint64(0)
+        _check(lib().vega_gpu_take(self.ctx._c, ctypes.c_uint64(self.h),
+                                   ctypes.c_uint64(num), _pp(k), _pp(v),
+                                   ctypes.byref(n)), "take", self.ctx._c)
+        return k[:n.value], v[:n.value]
+
+    def first(self):
+        """first row; raises VegaGpuError (empty collection) on an empty rdd"""
+        k = ctypes.c_int64()
+        v = self._vbox()
+        _check(lib().vega_gpu_first(self.ctx._c, ctypes.c_uint64(self.h),
+                                    ctypes.byref(k), ctypes.byref(v)),
+               "first", self.ctx._c)
+        return k.value, v.value
+
+    def is_empty(self):
+        e = ctypes.c_int(0)
+        _check(lib().vega_gpu_is_empty(self.ctx._c, ctypes.c_uint64(self.h),
+                                       ctypes.byref(e)), "is_empty", self.ctx._c)
+        return bool(e.value)
+
+    def _ordered(self, fn, what, num):
+        m = self._out_rows(num)
+        k = np.empty(m, dtype=np.int64)
+        v = np.empty(m, dtype=np.int64)
+        n = ctypes.c_uint64(0)
+        _check(fn(self.ctx._c, ctypes.c_uint64(self.h), ctypes.c_uint64(num),
+                  _pp(k), _pp(v), ctypes.byref(n)), what, self.ctx._c)
+        return k[:n.value], v[:n.value]
+
+    def take_ordered(self, num):
+        """min(num, n) lexicographically smallest rows, ascending"""
+        return self._ordered(lib().vega_gpu_take_ordered, "take_ordered", num)
+
+    def top(self, num):
+        """min(num, n) lexicographically largest rows, descending"""
+        return self._ordered(lib().vega_gpu_top, "top", num)
+
     def free(self):
         lib().vega_gpu_free_rdd(self.ctx._c, ctypes.c_uint64(self.h))
 
@@ -423,6 +514,49 @@ def dev_checksum(keys_t, vals_t, ws_t):
                                          _t(ws_t), ctypes.c_size_t(ws_t.numel())),
            "dev_checksum")
     return s.value
+
+
+def select_ws_bytes(num, cand_cap=0):
+    fn = lib().vega_dev_select_ws_bytes
+    fn.restype = ctypes.c_size_t
+    fn.argtypes = [ctypes.c_uint64, ctypes.c_uint64]
+    return int(fn(num, cand_cap))
+
+
+def dev_select_k(keys_t, vals_t, num, descending=False, cand_cap=0, ws_t=None):
+    """MSB radix select on device tensors: the min(num, n) smallest
+    (descending: largest) rows in order. Returns (out_k, out_v, passes);
+    ws_t defaults to a fresh workspace of select_ws_bytes(min(num, n))."""
+    import torch
+    n = keys_t.numel()
+    m = min(int(num), n)
+    if ws_t is None:
+        ws_t = torch.empty(select_ws_bytes(m, cand_cap), dtype=torch.uint8,
+                           device=keys_t.device)
+    out_k = torch.empty(m, dtype=torch.int64, device=keys_t.device)
+    out_v = torch.empty(m, dtype=torch.int64, device=keys_t.device)
+    nout = ctypes.c_uint64(0)
+    passes = ctypes.c_int(0)
+    _check(lib().vega_dev_select_k_i64(
+        _stream(), _t(keys_t), _t(vals_t), ctypes.c_uint64(n), ctypes.c_uint64(num),
+        ctypes.c_int(1 if descending else 0), ctypes.c_uint64(cand_cap),
+        _t(out_k), _t(out_v), ctypes.byref(nout), ctypes.byref(passes),
+        _t(ws_t), ctypes.c_size_t(ws_t.numel())), "dev_select_k")
+    return out_k[:nout.value], out_v[:nout.value], passes.value
+
+
+def dev_reduce_pairs(keys_t, vals_t, op, ws_t=None):
+    """column-wise reduce of device rows -> (k, v) on the host"""
+    import torch
+    if ws_t is None:
+        ws_t = torch.empty(1 << 16, dtype=torch.uint8, device=keys_t.device)
+    k = ctypes.c_int64()
+    v = ctypes.c_double() if op == OP_SUM_F64 else ctypes.c_int64()
+    _check(lib().vega_dev_reduce_pairs(
+        _stream(), _t(keys_t), _t(vals_t), ctypes.c_uint64(keys_t.numel()),
+        ctypes.c_int(op), ctypes.byref(k), ctypes.byref(v),
+        _t(ws_t), ctypes.c_size_t(ws_t.numel())), "dev_reduce_pairs")
+    return k.value, v.value
 
 
 def prof_enable(on=True):

@@ -4,6 +4,8 @@
  * tests/golden/, literals repeated here) plus a randomized reduce checked
  * against an in-binary std::map reference (independent of oracle/ — this
  * binary is test tooling for the C++ host layer). Exit 0 = all green.
+ * `vega_cli actions` runs the reference's action tests (fold, max/min, top,
+ * take_ordered, take, first, is_empty) the same way; prints `actions green`.
  * Without a GPU it must FAIL LOUDLY (nonzero, message) — there is no CPU
  * fallback anywhere in the product path.
  */
@@ -34,9 +36,98 @@ static pairs_t sorted(pairs_t v) {
     return v;
 }
 
+/* plain element RDD (the reference's Vec<i32> tests): element in the key
+ * column, value column 0 */
+static pairs_t elems(std::initializer_list<int64_t> xs) {
+    pairs_t out;
+    for (int64_t x : xs) out.push_back({x, 0});
+    return out;
+}
+static std::vector<int64_t> keys_of(const pairs_t &rows) {
+    std::vector<int64_t> out;
+    for (auto &r : rows) out.push_back(r.first);
+    return out;
+}
+
+/* `vega_cli actions`: the reference's action tests (tests/golden/actions.json)
+ * through the vega_core.hpp mirror */
+static int actions_main() {
+    using row_t = vega::PairRdd::row_t;
+    using keys_t = std::vector<int64_t>;
+    setvbuf(stdout, nullptr, _IONBF, 0);
+    try {
+        vega::Context sc;
+        /* fold (test_rdd.rs:114-121): (-1000..1000) in 10 partitions */
+        {
+            pairs_t in;
+            for (int64_t x = -1000; x < 1000; x++) in.push_back({x, 0});
+            auto rdd = sc.make_rdd(in, 10);
+            CHECK_EQ(rdd.fold({0, 0}), (row_t{-1000, 0}), "fold(0,+) == -1000 golden");
+            /* init is combined P+1 = 11 times (rdd.rs:311-322) */
+            CHECK_EQ(rdd.fold({5, 5}), (row_t{-1000 + 55, 55}), "fold(5,+) counts P+1 inits");
+            CHECK_EQ(rdd.aggregate({0, 0}), (row_t{-1000, 0}), "aggregate == fold");
+            CHECK_EQ(rdd.reduce().value(), (row_t{-1000, 0}), "reduce(+) == -1000");
+        }
+        /* max / min (test_rdd.rs:599-608) */
+        {
+            auto rdd = sc.parallelize(elems({13, 28, 3, 4, 51, 103, 12, 113, 19}), 2);
+            CHECK_EQ(rdd.max().value(), (row_t{113, 0}), "max golden");
+            CHECK_EQ(rdd.min().value(), (row_t{3, 0}), "min golden");
+        }
+        /* top / take_ordered (test_rdd.rs:655-673) */
+        {
+            auto rdd = sc.parallelize(elems({13, 28, 3, 4, 51, 108, 12, 113, 19}), 4);
+            CHECK_EQ(keys_of(rdd.top(3)), (keys_t{113, 108, 51}), "top(3) golden");
+            CHECK_EQ(keys_of(rdd.take_ordered(3)), (keys_t{3, 4, 12}), "take_ordered(3) golden");
+            CHECK_EQ(rdd.top(0).size(), (size_t)0, "top(0) empty");
+            CHECK_EQ(rdd.take_ordered(100).size(), (size_t)9, "take_ordered(num > n) == n rows");
+        }
+        /* take (test_rdd.rs:179-198) */
+        {
+            auto rdd = sc.parallelize(elems({1, 2, 3, 4, 5, 6}), 4);
+            CHECK_EQ(rdd.take(1).size(), (size_t)1, "take(1) golden");
+            CHECK_EQ(keys_of(rdd.take(3)), (keys_t{1, 2, 3}), "take(3) golden (row prefix)");
+            CHECK_EQ(rdd.take(7).size(), (size_t)6, "take(7) golden");
+            auto empty = sc.parallelize({}, 4);
+            CHECK_EQ(empty.take(1).size(), (size_t)0, "take(1) on empty golden");
+        }
+        /* first (test_rdd.rs:201-213) */
+        {
+            auto rdd = sc.parallelize(elems({1, 2, 3, 4}), 4);
+            CHECK_EQ(rdd.first(), (row_t{1, 0}), "first golden");
+            auto empty = sc.parallelize({}, 4);
+            bool threw = false;
+            try {
+                (void)empty.first();
+            } catch (const vega::VegaError &e) {
+                threw = strstr(e.what(), "empty collection") != nullptr;
+            }
+            CHECK_EQ(threw, true, "first on empty is Err(empty collection) golden");
+        }
+        /* is_empty (test_rdd.rs:590-596); None on empty for the Option actions */
+        {
+            auto empty = sc.parallelize({}, 1);
+            CHECK_EQ(empty.is_empty(), true, "is_empty golden");
+            CHECK_EQ(empty.reduce().has_value(), false, "reduce on empty is None");
+            CHECK_EQ(empty.max().has_value(), false, "max on empty is None");
+            CHECK_EQ(empty.fold({5, 7}), (row_t{10, 14}), "fold on empty == (P+1)*init");
+        }
+    } catch (const std::exception &e) {
+        fprintf(stderr, "vega_cli: FATAL: %s\n", e.what());
+        return 1;
+    }
+    if (fails) {
+        fprintf(stderr, "vega_cli: %d check(s) FAILED\n", fails);
+        return 1;
+    }
+    printf("vega_cli: actions green\n");
+    return 0;
+}
+
 int main(int argc, char **argv) {
+    if (argc >= 2 && strcmp(argv[1], "actions") == 0) return actions_main();
     if (argc < 2 || strcmp(argv[1], "selftest") != 0) {
-        fprintf(stderr, "usage: vega_cli selftest\n");
+        fprintf(stderr, "usage: vega_cli selftest|actions\n");
         return 2;
     }
     setvbuf(stdout, nullptr, _IONBF, 0); /* keep progress visible on a crash */

@@ -5,14 +5,17 @@
  * SURVEY.md §0), so this is the compiled-host embodiment of the same API
  * semantics: Context (context.rs:147-164), make_rdd/parallelize
  * (context.rs:406-442), PairRdd ops (pair_rdd.rs:20-171), actions
- * collect/count (rdd.rs:420-447). Same names, same argument meaning, same
+ * collect/count (rdd.rs:420-447) and reduce/fold/aggregate/min/max/take/
+ * first/is_empty/top/take_ordered. Same names, same argument meaning, same
  * error behavior (throws on failure — the reference Results/panics).
  *
  * Header-only; link against libvega_gpu.so.
  */
 #pragma once
 
+#include <algorithm>
 #include <cstdint>
+#include <optional>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -112,6 +115,71 @@ class PairRdd {
         for (uint64_t i = 0; i < n; i++) out[i] = {k[i], v[i]};
         return out;
     }
+    /* device-side actions (i64-valued rows; rdd.rs names). Option<T> of the
+     * reference = std::optional; Err = VegaError. */
+    using row_t = std::pair<int64_t, int64_t>;
+    /* rdd.rs:274-291: column-wise (k1 op k2, v1 op v2); nullopt on empty */
+    std::optional<row_t> reduce(vega_op_t op = VEGA_OP_SUM_I64) const {
+        int64_t k = 0, v = 0;
+        int ne = 0;
+        check(vega_gpu_reduce(c_, h_, op, &k, &v, &ne), "reduce", c_);
+        return ne ? std::optional<row_t>(row_t{k, v}) : std::nullopt;
+    }
+    /* rdd.rs:311-322: init is combined num_splits+1 times */
+    row_t fold(row_t init, vega_op_t op = VEGA_OP_SUM_I64) const {
+        int64_t k = 0, v = 0;
+        check(vega_gpu_fold(c_, h_, op, init.first, &init.second, &k, &v), "fold", c_);
+        return {k, v};
+    }
+    /* aggregate(init, seq, comb) collapses to fold under the fixed op enum */
+    row_t aggregate(row_t init, vega_op_t op = VEGA_OP_SUM_I64) const { return fold(init, op); }
+    /* rdd.rs:1081-1099: lexicographic (Ord for (i64, i64)) extremes */
+    std::optional<row_t> min() const {
+        int64_t k = 0, v = 0;
+        int ne = 0;
+        check(vega_gpu_min(c_, h_, &k, &v, &ne), "min", c_);
+        return ne ? std::optional<row_t>(row_t{k, v}) : std::nullopt;
+    }
+    std::optional<row_t> max() const {
+        int64_t k = 0, v = 0;
+        int ne = 0;
+        check(vega_gpu_max(c_, h_, &k, &v, &ne), "max", c_);
+        return ne ? std::optional<row_t>(row_t{k, v}) : std::nullopt;
+    }
+    /* rdd.rs:565-620 */
+    std::vector<row_t> take(uint64_t num) const {
+        uint64_t m = std::min<uint64_t>(num, count()), n = 0;
+        std::vector<int64_t> k(m), v(m);
+        check(vega_gpu_take(c_, h_, num, k.data(), v.data(), &n), "take", c_);
+        return zip(k, v, n);
+    }
+    /* rdd.rs:534-543: Err("empty collection") on an empty rdd */
+    row_t first() const {
+        int64_t k = 0, v = 0;
+        check(vega_gpu_first(c_, h_, &k, &v), "first", c_);
+        return {k, v};
+    }
+    /* rdd.rs:1073-1078 */
+    bool is_empty() const {
+        int e = 0;
+        check(vega_gpu_is_empty(c_, h_, &e), "is_empty", c_);
+        return e != 0;
+    }
+    /* rdd.rs:1124-1153: smallest rows ascending */
+    std::vector<row_t> take_ordered(uint64_t num) const {
+        uint64_t m = std::min<uint64_t>(num, count()), n = 0;
+        std::vector<int64_t> k(m), v(m);
+        check(vega_gpu_take_ordered(c_, h_, num, k.data(), v.data(), &n), "take_ordered", c_);
+        return zip(k, v, n);
+    }
+    /* rdd.rs:1106-1117: largest rows descending */
+    std::vector<row_t> top(uint64_t num) const {
+        uint64_t m = std::min<uint64_t>(num, count()), n = 0;
+        std::vector<int64_t> k(m), v(m);
+        check(vega_gpu_top(c_, h_, num, k.data(), v.data(), &n), "top", c_);
+        return zip(k, v, n);
+    }
+
     void free() {
         if (c_ && h_) vega_gpu_free_rdd(c_, h_);
         h_ = 0;
@@ -119,6 +187,13 @@ class PairRdd {
     vega_rdd_t handle() const { return h_; }
 
   private:
+    static std::vector<std::pair<int64_t, int64_t>> zip(const std::vector<int64_t> &k,
+                                                        const std::vector<int64_t> &v,
+                                                        uint64_t n) {
+        std::vector<std::pair<int64_t, int64_t>> out(n);
+        for (uint64_t i = 0; i < n; i++) out[i] = {k[i], v[i]};
+        return out;
+    }
     vega_ctx_t *c_ = nullptr;
     vega_rdd_t h_ = 0;
     bool f64_ = false;
