@@ -332,6 +332,100 @@ def test_dev_partition_range_torch(ctx):
     assert (ov.cpu().numpy() == rv).all()
 
 
+# ---- partition edges: small, ragged n; exact keys, values (= row index, so
+# ---- within-bucket order is pinned) and counts against the CPU reference
+
+PART_N = 12_289  # three tiles and one row
+
+
+def _partition_input():
+    rng = np.random.RandomState(301)
+    pool = rng.randint(-2**63, 2**63 - 1, size=2000, dtype=np.int64)
+    k = pool[rng.randint(0, len(pool), size=PART_N)]  # ~6 rows per key
+    return k, np.arange(PART_N, dtype=np.int64)
+
+
+@pytest.mark.parametrize("nparts", [1, 2, 3, 255, 256])
+def test_dev_partition_nparts_edges(ctx, nparts):
+    import torch
+    from vega_amd import gpu, shuffle
+    hk, hv = _partition_input()
+    k = torch.from_numpy(hk).cuda()
+    v = torch.from_numpy(hv).cuda()
+    ok = torch.empty_like(k)
+    ov = torch.empty_like(v)
+    counts = gpu.dev_partition(k, v, nparts, ok, ov, gpu.alloc_ws(PART_N))
+    rk, rv, rcounts = shuffle.partition_cpu(hk, hv, nparts)
+    assert (counts.astype(np.int64) == rcounts).all()
+    assert (ok.cpu().numpy() == rk).all()
+    assert (ov.cpu().numpy() == rv).all(), "rows of a bucket out of row order"
+
+
+@pytest.mark.parametrize("nparts", [0, 257])
+def test_dev_partition_rejects_bad_nparts(ctx, nparts):
+    """an error, and neither the device outputs nor the counts are touched"""
+    import ctypes
+    import torch
+    from vega_amd import gpu
+    hk, hv = _partition_input()
+    k = torch.from_numpy(hk).cuda()
+    v = torch.from_numpy(hv).cuda()
+    ok = torch.full_like(k, -77)
+    ov = torch.full_like(v, -78)
+    counts = np.full(512, 0xABCD, dtype=np.uint64)
+    ws = gpu.alloc_ws(PART_N)
+    rc = gpu.lib().vega_dev_partition_i64(
+        gpu._stream(), gpu._t(k), gpu._t(v), ctypes.c_uint64(PART_N),
+        ctypes.c_uint32(nparts), gpu._t(ok), gpu._t(ov), gpu._pp(counts),
+        gpu._t(ws), ctypes.c_size_t(ws.numel()))
+    torch.cuda.synchronize()
+    assert rc != 0
+    assert (counts == 0xABCD).all()
+    assert (ok == -77).all().item() and (ov == -78).all().item()
+    with pytest.raises(gpu.VegaGpuError):
+        gpu.dev_partition(k, v, nparts, ok, ov, ws)
+
+
+I64_LO, I64_HI = -2**63, 2**63 - 1
+
+RANGE_CASES = {
+    # duplicate splitters (empty buckets between them), one of them (10)
+    # equal to a third of all keys, and the extreme keys on both sides
+    "duplicate_splitters": (
+        [-5, 10, 10, 10, 1000, 1000, 2**40],
+        [I64_LO, -6, -5, -4, 9, 10, 10, 10, 10, 10, 10, 11, 999, 1000, 1001,
+         2**40 - 1, 2**40, I64_HI]),
+    "extreme_splitters": ([I64_LO, 0, I64_HI], [I64_LO, I64_LO + 1, -1, 0, 1, I64_HI - 1, I64_HI]),
+    "all_in_first_bucket": ([1000, 2000, 3000], list(range(-100, 100)) + [I64_LO]),
+    "all_in_last_bucket": ([-3000, -2000, -1000], list(range(-100, 100)) + [-1000, I64_HI]),
+}
+
+
+@pytest.mark.parametrize("case", sorted(RANGE_CASES))
+def test_dev_partition_range_edges(ctx, case):
+    import torch
+    from vega_amd import gpu, shuffle
+    spl_list, key_pool = RANGE_CASES[case]
+    spl_np = np.asarray(spl_list, dtype=np.int64)
+    pool = np.asarray(key_pool, dtype=np.int64)
+    hk = pool[np.random.RandomState(302).randint(0, len(pool), size=PART_N)]
+    hv = np.arange(PART_N, dtype=np.int64)
+    k = torch.from_numpy(hk).cuda()
+    v = torch.from_numpy(hv).cuda()
+    ok = torch.empty_like(k)
+    ov = torch.empty_like(v)
+    counts = gpu.dev_partition_range(k, v, torch.from_numpy(spl_np).cuda(), ok, ov,
+                                     gpu.alloc_ws(PART_N))
+    rk, rv, rcounts = shuffle.partition_range_cpu(hk, hv, spl_np)
+    if case == "all_in_first_bucket":
+        assert rcounts[0] == PART_N
+    if case == "all_in_last_bucket":
+        assert rcounts[-1] == PART_N
+    assert (counts.astype(np.int64) == rcounts).all()
+    assert (ok.cpu().numpy() == rk).all()
+    assert (ov.cpu().numpy() == rv).all(), "rows of a bucket out of row order"
+
+
 def test_checksum_matches_oracle(ctx):
     import torch
     from vega_amd import gpu
