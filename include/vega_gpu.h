@@ -67,6 +67,8 @@ typedef enum {
     VEGA_PRED_VAL_GT       = 1, /* keep if v > p0 */
     VEGA_PRED_KEY_IN_RANGE = 2, /* keep if p0 <= k < p1 */
 } vega_pred_t;
+/* columns of the stats_by_key combiner C = (count, sum, min, max) */
+typedef enum { VEGA_STAT_COUNT = 0, VEGA_STAT_SUM = 1, VEGA_STAT_MIN = 2, VEGA_STAT_MAX = 3 } vega_stat_t;
 
 typedef struct vega_ctx vega_ctx_t;
 typedef uint64_t vega_rdd_t;      /* opaque RDD handle, 0 = invalid */
@@ -150,6 +152,27 @@ int vega_gpu_subtract(vega_ctx_t *ctx, vega_rdd_t a, vega_rdd_t b,
  * counts over the VALUE column; result rows are (value, count) */
 int vega_gpu_count_by_value(vega_ctx_t *ctx, vega_rdd_t rdd, uint32_t nparts,
                             vega_rdd_t *out);
+/* combine_by_key (pair_rdd.rs:20-33) with C = (count, sum, min, max) over i64
+ * values: create |v| (1, v, v, v), merge_value / merge_combiners field-wise
+ * +, wrapping +, min, max. One grouping sort and one segmented pass yield all
+ * four columns. Input: a plain pair rdd with i64 values, not modified (f64
+ * values: VEGA_ERR_UNSUPPORTED; grouped / join-result / stats handles:
+ * VEGA_ERR_INVALID; ngpus > 1 context: VEGA_ERR_UNSUPPORTED). Rows come in
+ * grouping order, unspecified as for reduce_by_key.
+ * The result is a STATS rdd: keys plus the four columns, collected with
+ * vega_gpu_collect_stats. Its key and count columns sit where a plain rdd
+ * keeps keys and values, so an entry that does not know the kind sees a valid
+ * (key, count) pair rdd of as many rows as there are keys; the device-side
+ * actions reject it like a join result. vega_gpu_count returns the number of
+ * keys, vega_gpu_free_rdd frees all five columns. */
+int vega_gpu_stats_by_key(vega_ctx_t *ctx, vega_rdd_t rdd, uint32_t nparts, vega_rdd_t *out);
+/* keys == NULL queries *nk; all five arrays sized *nk, rows aligned across columns */
+int vega_gpu_collect_stats(vega_ctx_t *ctx, vega_rdd_t stats, int64_t *keys, int64_t *count,
+                           int64_t *sum, int64_t *min, int64_t *max, uint64_t *nk);
+/* map_values(|c| c.<which>): a PLAIN (key, column) pair rdd, device copy, same
+ * row order — usable by every op and action. Not a stats rdd, or a which
+ * outside vega_stat_t: VEGA_ERR_INVALID. */
+int vega_gpu_stats_column(vega_ctx_t *ctx, vega_rdd_t stats, vega_stat_t which, vega_rdd_t *out);
 
 /* narrow transforms (device-resident; stable order for filter) */
 int vega_gpu_map(vega_ctx_t *ctx, vega_rdd_t rdd, vega_map_op_t op, int64_t p0,
@@ -264,6 +287,18 @@ int vega_dev_partition_range_i64(void *stream, const int64_t *keys, const int64_
 int vega_dev_sort_reduce(void *stream, const int64_t *in_k, const void *in_v,
                          uint64_t n, int op, int64_t *out_k, void *out_v,
                          uint64_t *h_nout, void *d_ws, size_t ws_bytes);
+
+/* the same grouping sort followed by the fused (count, sum, min, max)
+ * aggregate of vega_gpu_stats_by_key, on the rows a rank received from the
+ * exchange (raw rows; no map-side pre-combine). in_k/in_v are NOT modified.
+ * The five out arrays must hold n rows each and be 16-byte aligned (the
+ * all-distinct path stores pairs), else VEGA_ERR_INVALID. d_ws must hold
+ * vega_dev_ws_bytes(n) bytes, else VEGA_ERR_CAP. *h_nout = #distinct keys
+ * (host, after an internal sync). */
+int vega_dev_sort_stats_i64(void *stream, const int64_t *in_k, const int64_t *in_v, uint64_t n,
+                            int64_t *out_k, int64_t *out_count, int64_t *out_sum,
+                            int64_t *out_min, int64_t *out_max, uint64_t *h_nout,
+                            void *d_ws, size_t ws_bytes);
 
 /* stable LSB radix sort by signed-i64 key (sort_by_key). In-place semantics:
  * result lands back in keys/vals. */

@@ -35,6 +35,12 @@ struct RddImpl {
      * u64 offsets (n+1), d_v2 = values in grouped order (n2 rows) */
     bool grouped = false;
     uint64_t n2 = 0;
+    /* stats rdd (stats_by_key): d_k = distinct keys (n of them), d_v = count
+     * column, d_v2 = sum, d_min / d_max the other two — an entry that never
+     * looks at the kind sees a valid (key, count) pair rdd of n rows */
+    bool stats = false;
+    void *d_min = nullptr;
+    void *d_max = nullptr;
     /* multi-GPU (ngpus > 1): per-device shards; d_k/d_v above are device 0's
      * shard so the single-GPU code paths stay untouched for G == 1 */
     std::vector<int64_t *> mk;
@@ -154,6 +160,8 @@ static void free_rdd_buffers(vega_ctx *c, RddImpl *r) {
         if (r->d_v) (void)hipFree(r->d_v);
     }
     if (r->d_v2) (void)hipFree(r->d_v2);
+    if (r->d_min) (void)hipFree(r->d_min);
+    if (r->d_max) (void)hipFree(r->d_max);
 }
 
 int vega_gpu_shutdown(vega_ctx_t *c) {
@@ -1158,6 +1166,100 @@ int vega_gpu_top(vega_ctx_t *c, vega_rdd_t rdd, uint64_t num, int64_t *keys, int
     return ordered_common(c, rdd, num, true, keys, vals, n_out);
 }
 
+/* ---------------- stats_by_key ---------------- */
+/* combine_by_key (pair_rdd.rs:20-33) with the combiner C = (count, sum, min,
+ * max) over i64 values: create |v| (1, v, v, v), merge field-wise +, wrapping
+ * +, min, max. One grouping sort and one segmented pass for all four columns
+ * (four reduce_by_key calls would pay the sort four times). */
+int vega_gpu_stats_by_key(vega_ctx_t *c, vega_rdd_t rdd, uint32_t nparts, vega_rdd_t *out) {
+    if (!c || !out) return VEGA_ERR_INVALID;
+    if (c->ngpus > 1) return VEGA_ERR_UNSUPPORTED; /* G>1: north-star ops only */
+    RddImpl *r = get_rdd(c, rdd);
+    if (!r || r->grouped || r->d_v2) return VEGA_ERR_INVALID; /* plain pair handles only */
+    if (r->vtype != 0) {
+        snprintf(c->err, sizeof c->err,
+                 "stats_by_key: f64 values are not supported (i64 values only)");
+        return VEGA_ERR_UNSUPPORTED;
+    }
+    int rc = ensure_ws(c, r->n);
+    if (rc) return rc;
+    RddImpl *o;
+    rc = new_rdd(c, r->n ? r->n : 1, 0, nparts, &o, out);
+    if (rc) return rc;
+    o->stats = true;
+    const size_t bytes = (size_t)(r->n ? r->n : 1) * 8;
+    Ws ws(c->ws, c->ws_bytes);
+    uint64_t nout = 0;
+    hipError_t e = hipMalloc(&o->d_v2, bytes);
+    if (e == hipSuccess) e = hipMalloc(&o->d_min, bytes);
+    if (e == hipSuccess) e = hipMalloc(&o->d_max, bytes);
+    if (e == hipSuccess)
+        e = group_sort_stats(c->stream, (const uint64_t *)r->d_k, (const uint64_t *)r->d_v,
+                             r->n, o->d_k, (int64_t *)o->d_v, (int64_t *)o->d_v2,
+                             (int64_t *)o->d_min, (int64_t *)o->d_max, &nout, ws);
+    if (e != hipSuccess) { /* no half-built handle is handed out */
+        vega_gpu_free_rdd(c, *out);
+        *out = 0;
+        snprintf(c->err, sizeof c->err, "stats_by_key: %s", hipGetErrorString(e));
+        if (e == hipErrorNotSupported) return VEGA_ERR_UNSUPPORTED;
+        return e == hipErrorOutOfMemory ? VEGA_ERR_NOMEM : VEGA_ERR_HIP;
+    }
+    o->n = nout;
+    return VEGA_OK;
+}
+
+int vega_gpu_collect_stats(vega_ctx_t *c, vega_rdd_t stats, int64_t *keys, int64_t *count,
+                           int64_t *sum, int64_t *min, int64_t *max, uint64_t *nk) {
+    if (!c || !nk) return VEGA_ERR_INVALID;
+    RddImpl *r = get_rdd(c, stats);
+    if (!r || !r->stats) return VEGA_ERR_INVALID;
+    if (!keys) { *nk = r->n; return VEGA_OK; }
+    if (*nk < r->n) return VEGA_ERR_CAP;
+    *nk = r->n;
+    if (r->n) {
+        if (!count || !sum || !min || !max) return VEGA_ERR_INVALID;
+        const size_t bytes = (size_t)r->n * 8;
+        CTX_TRY(c, hipMemcpyAsync(keys, r->d_k, bytes, hipMemcpyDeviceToHost, c->stream));
+        CTX_TRY(c, hipMemcpyAsync(count, r->d_v, bytes, hipMemcpyDeviceToHost, c->stream));
+        CTX_TRY(c, hipMemcpyAsync(sum, r->d_v2, bytes, hipMemcpyDeviceToHost, c->stream));
+        CTX_TRY(c, hipMemcpyAsync(min, r->d_min, bytes, hipMemcpyDeviceToHost, c->stream));
+        CTX_TRY(c, hipMemcpyAsync(max, r->d_max, bytes, hipMemcpyDeviceToHost, c->stream));
+    }
+    CTX_TRY(c, hipStreamSynchronize(c->stream));
+    return VEGA_OK;
+}
+
+/* map_values(|c| c.<which>): a plain (key, column) pair rdd, device copy */
+int vega_gpu_stats_column(vega_ctx_t *c, vega_rdd_t stats, vega_stat_t which, vega_rdd_t *out) {
+    if (!c || !out) return VEGA_ERR_INVALID;
+    RddImpl *r = get_rdd(c, stats);
+    if (!r || !r->stats) return VEGA_ERR_INVALID;
+    const void *col = nullptr;
+    switch ((int)which) {
+    case VEGA_STAT_COUNT: col = r->d_v; break;
+    case VEGA_STAT_SUM: col = r->d_v2; break;
+    case VEGA_STAT_MIN: col = r->d_min; break;
+    case VEGA_STAT_MAX: col = r->d_max; break;
+    default: return VEGA_ERR_INVALID;
+    }
+    RddImpl *o;
+    int rc = new_rdd(c, r->n ? r->n : 1, 0, r->nparts, &o, out);
+    if (rc) return rc;
+    o->n = r->n;
+    if (r->n) {
+        hipError_t e = hipMemcpyAsync(o->d_k, r->d_k, r->n * 8, hipMemcpyDeviceToDevice, c->stream);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(o->d_v, col, r->n * 8, hipMemcpyDeviceToDevice, c->stream);
+        if (e != hipSuccess) { /* no half-filled handle is handed out */
+            vega_gpu_free_rdd(c, *out);
+            *out = 0;
+            snprintf(c->err, sizeof c->err, "stats_column: %s", hipGetErrorString(e));
+            return VEGA_ERR_HIP;
+        }
+    }
+    return VEGA_OK;
+}
+
 int vega_gpu_free_rdd(vega_ctx_t *c, vega_rdd_t rdd) {
     auto it = c->rdds.find(rdd);
     if (it == c->rdds.end()) return VEGA_ERR_INVALID;
@@ -1228,6 +1330,31 @@ int vega_dev_sort_reduce(void *stream, const int64_t *in_k, const void *in_v,
     hipError_t e = group_sort_reduce((hipStream_t)stream, (const uint64_t *)in_k,
                                      (const uint64_t *)in_v, n, op,
                                      (uint64_t *)out_k, out_v, h_nout, ws);
+    if (e == hipErrorNotSupported) return VEGA_ERR_UNSUPPORTED;
+    return e == hipSuccess ? VEGA_OK : (e == hipErrorOutOfMemory ? VEGA_ERR_NOMEM : VEGA_ERR_HIP);
+}
+
+/* reduce-side grouping + fused (count, sum, min, max) aggregate; see
+ * vega_gpu.h. The five outputs take 16-B pair stores on the all-distinct
+ * fast path, hence the alignment requirement. */
+int vega_dev_sort_stats_i64(void *stream, const int64_t *in_k, const int64_t *in_v, uint64_t n,
+                            int64_t *out_k, int64_t *out_count, int64_t *out_sum,
+                            int64_t *out_min, int64_t *out_max, uint64_t *h_nout,
+                            void *d_ws, size_t ws_bytes) {
+    if (!h_nout) return VEGA_ERR_INVALID;
+    *h_nout = 0;
+    if (n >= (1ULL << 32)) return VEGA_ERR_UNSUPPORTED;
+    if (!n) return VEGA_OK;
+    if (!in_k || !in_v || !out_k || !out_count || !out_sum || !out_min || !out_max)
+        return VEGA_ERR_INVALID;
+    if ((((uintptr_t)out_k | (uintptr_t)out_count | (uintptr_t)out_sum |
+          (uintptr_t)out_min | (uintptr_t)out_max) & 15) != 0)
+        return VEGA_ERR_INVALID;
+    if (!d_ws || ws_bytes < ws_bytes_for(n)) return VEGA_ERR_CAP;
+    Ws ws(d_ws, ws_bytes);
+    hipError_t e = group_sort_stats((hipStream_t)stream, (const uint64_t *)in_k,
+                                    (const uint64_t *)in_v, n, out_k, out_count, out_sum,
+                                    out_min, out_max, h_nout, ws);
     if (e == hipErrorNotSupported) return VEGA_ERR_UNSUPPORTED;
     return e == hipSuccess ? VEGA_OK : (e == hipErrorOutOfMemory ? VEGA_ERR_NOMEM : VEGA_ERR_HIP);
 }

@@ -79,6 +79,21 @@ hipError_t group_sort_reduce(hipStream_t s, const uint64_t *in_k, const uint64_t
                              uint64_t n, int op, uint64_t *out_k, void *out_v,
                              uint64_t *h_nout, Ws &ws);
 
+/* fused multi-aggregate over key-sorted i64 rows: per equal-key run one row
+ * of (key, count, wrapping sum, min, max) in five SoA columns, each holding
+ * up to n rows. packed: rows are interleaved 16-B (k,v) pairs at k. Returns
+ * #segments in *h_nout (after stream sync). */
+hipError_t seg_stats(hipStream_t s, const uint64_t *k, const uint64_t *v, uint64_t n,
+                     int64_t *out_k, int64_t *out_count, int64_t *out_sum,
+                     int64_t *out_min, int64_t *out_max, uint64_t *h_nout, Ws &ws,
+                     bool packed = false);
+
+/* grouping sort (as group_sort_reduce runs it) + seg_stats */
+hipError_t group_sort_stats(hipStream_t s, const uint64_t *in_k, const uint64_t *in_v,
+                            uint64_t n, int64_t *out_k, int64_t *out_count,
+                            int64_t *out_sum, int64_t *out_min, int64_t *out_max,
+                            uint64_t *h_nout, Ws &ws);
+
 /* hash-mod partition scatter; h_counts on host after sync */
 hipError_t hash_partition(hipStream_t s, const uint64_t *in_k, const uint64_t *in_v,
                           uint64_t n, uint32_t nparts, uint64_t *out_k, uint64_t *out_v,

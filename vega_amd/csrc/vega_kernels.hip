@@ -1778,6 +1778,256 @@ hipError_t group_sort_reduce(hipStream_t s, const uint64_t *in_k, const uint64_t
 }
 
 /* ------------------------------------------------------------------ */
+/* fused multi-aggregate: combine_by_key with C = (count, sum, min, max) */
+
+struct StatsAcc {
+    int64_t cnt, mn, mx;
+    uint64_t sum; /* wrapping */
+    __device__ __forceinline__ void reset() { cnt = 0; sum = 0; mn = INT64_MAX; mx = INT64_MIN; }
+    __device__ __forceinline__ void add(uint64_t v) {
+        int64_t x = (int64_t)v;
+        cnt += 1;
+        sum += v;
+        mn = x < mn ? x : mn;
+        mx = x > mx ? x : mx;
+    }
+};
+
+/* Sibling of k_seg_emit<OP,PK> for i64 values: same geometry (SEG_B threads x
+ * SEG_IPT-row chunks, register-only, 16-B loads), same block-exclusive head
+ * scan seeded from head_base[blockIdx.x], same store / atomic discipline —
+ * with four accumulators per run and five SoA outputs. All four fields are
+ * integer, so any flush order gives the same bits: atomics are the only
+ * inter-block traffic, nothing waits on another block. out_count / out_sum
+ * must be zeroed, out_min / out_max filled with INT64_MAX / INT64_MIN. */
+template <bool PK>
+__global__ __launch_bounds__(SEG_B) void k_seg_stats(
+    const uint64_t *__restrict__ k, const uint64_t *__restrict__ v, uint64_t n,
+    const uint32_t *__restrict__ head_base, int64_t *__restrict__ out_k,
+    int64_t *__restrict__ out_count, int64_t *__restrict__ out_sum,
+    int64_t *__restrict__ out_min, int64_t *__restrict__ out_max) {
+    __shared__ uint32_t wsc[SEG_B / 64];
+
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const uint64_t tbase = (uint64_t)blockIdx.x * TILE;
+    const uint64_t c0g = tbase + (uint64_t)t * SEG_IPT; /* chunk start, global */
+
+    uint64_t kk[SEG_IPT], sv[SEG_IPT];
+    if (c0g + SEG_IPT <= n) { /* interior chunk: unguarded 16-B vector loads */
+        if (PK) {
+            const ulonglong2 *rp = reinterpret_cast<const ulonglong2 *>(k) + c0g;
+#pragma unroll
+            for (int j = 0; j < SEG_IPT; ++j) {
+                ulonglong2 r2 = rp[j];
+                kk[j] = r2.x;
+                sv[j] = r2.y;
+            }
+        } else {
+            const ulonglong2 *kp = reinterpret_cast<const ulonglong2 *>(k + c0g);
+            const ulonglong2 *vp = reinterpret_cast<const ulonglong2 *>(v + c0g);
+#pragma unroll
+            for (int j2 = 0; j2 < SEG_IPT / 2; ++j2) {
+                ulonglong2 t2 = kp[j2];
+                ulonglong2 u2 = vp[j2];
+                kk[2 * j2] = t2.x;
+                kk[2 * j2 + 1] = t2.y;
+                sv[2 * j2] = u2.x;
+                sv[2 * j2 + 1] = u2.y;
+            }
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < SEG_IPT; ++j) {
+            uint64_t gi = c0g + j;
+            kk[j] = (gi < n) ? k[PK ? 2 * gi : gi] : ~0ULL;
+            sv[j] = (gi < n) ? (PK ? k[2 * gi + 1] : v[gi]) : 0;
+        }
+    }
+    uint64_t prev = (c0g > 0 && c0g <= n) ? k[PK ? 2 * (c0g - 1) : c0g - 1] : 0;
+
+    /* count heads in the chunk */
+    uint32_t cnt = 0;
+#pragma unroll
+    for (int j = 0; j < SEG_IPT; ++j) {
+        uint64_t gi = c0g + j;
+        if (gi < n) {
+            uint64_t pk = (j > 0) ? kk[j - 1] : prev;
+            cnt += (gi == 0) || (kk[j] != pk);
+        }
+    }
+    /* block exclusive scan of cnt */
+    uint32_t inc = cnt;
+    for (int off = 1; off < 64; off <<= 1) {
+        uint32_t u = __shfl_up(inc, off);
+        if (lane >= off) inc += u;
+    }
+    if (lane == 63) wsc[w] = inc;
+    __syncthreads();
+    uint32_t excl = inc - cnt;
+    for (int i = 0; i < w; ++i) excl += wsc[i];
+
+    /* Fast path: a fully-distinct interior chunk whose last run does not
+     * continue emits its length-1 runs (1, v, v, v) with pure vector stores */
+    bool fast = false;
+    if (cnt == SEG_IPT && c0g + SEG_IPT <= n) {
+        uint64_t nk = (c0g + SEG_IPT < n) ? k[PK ? 2 * (c0g + SEG_IPT) : c0g + SEG_IPT] : ~kk[SEG_IPT - 1];
+        fast = (nk != kk[SEG_IPT - 1]);
+    }
+    int64_t segid = (int64_t)head_base[blockIdx.x] + excl - 1;
+    StatsAcc a;
+    a.reset();
+    bool have = false, started_here = false;
+    if (fast) {
+        int64_t s0 = segid + 1;
+        if ((s0 & 1) == 0) {
+            ulonglong2 *ok2 = (ulonglong2 *)(out_k + s0);
+            ulonglong2 *oc2 = (ulonglong2 *)(out_count + s0);
+            ulonglong2 *os2 = (ulonglong2 *)(out_sum + s0);
+            ulonglong2 *on2 = (ulonglong2 *)(out_min + s0);
+            ulonglong2 *ox2 = (ulonglong2 *)(out_max + s0);
+#pragma unroll
+            for (int j = 0; j < SEG_IPT / 2; ++j) {
+                ulonglong2 v2 = make_ulonglong2(sv[2 * j], sv[2 * j + 1]);
+                ok2[j] = make_ulonglong2(kk[2 * j], kk[2 * j + 1]);
+                oc2[j] = make_ulonglong2(1, 1);
+                os2[j] = v2;
+                on2[j] = v2;
+                ox2[j] = v2;
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < SEG_IPT; ++j) {
+                out_k[s0 + j] = (int64_t)kk[j];
+                out_count[s0 + j] = 1;
+                out_sum[s0 + j] = (int64_t)sv[j];
+                out_min[s0 + j] = (int64_t)sv[j];
+                out_max[s0 + j] = (int64_t)sv[j];
+            }
+        }
+        /* have stays false: inert in the wave tail-combine below */
+    } else
+#pragma unroll
+    for (int j = 0; j < SEG_IPT; ++j) {
+        uint64_t gi = c0g + j;
+        if (gi >= n) break;
+        uint64_t key = kk[j];
+        uint64_t pk = (j > 0) ? kk[j - 1] : prev;
+        bool head = (gi == 0) || (key != pk);
+        if (head) {
+            if (have) { /* previous run terminated by this head */
+                if (started_here) { /* exclusive: plain stores */
+                    out_count[segid] = a.cnt;
+                    out_sum[segid] = (int64_t)a.sum;
+                    out_min[segid] = a.mn;
+                    out_max[segid] = a.mx;
+                } else { /* open at the chunk's start: shared with earlier chunks */
+                    atomicAdd((unsigned long long *)(out_count + segid), (unsigned long long)a.cnt);
+                    atomicAdd((unsigned long long *)(out_sum + segid), (unsigned long long)a.sum);
+                    atomicMin((long long *)(out_min + segid), (long long)a.mn);
+                    atomicMax((long long *)(out_max + segid), (long long)a.mx);
+                }
+            }
+            segid++;
+            out_k[segid] = (int64_t)key;
+            a.reset();
+            started_here = true;
+        }
+        have = true;
+        a.add(sv[j]);
+    }
+    /* Tail flush; head-free chunks of one long run are first combined within
+     * the wave (segmented inclusive shfl-scan over the contiguous equal-segid
+     * lanes): one group of four atomics per run per wave, not per lane. */
+    long long sid = (have && cnt == 0) ? (long long)segid : -(long long)(lane + 2);
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        long long s2 = __shfl_up(sid, off);
+        long long c2 = __shfl_up((long long)a.cnt, off);
+        long long u2 = __shfl_up((long long)a.sum, off);
+        long long n2 = __shfl_up((long long)a.mn, off);
+        long long x2 = __shfl_up((long long)a.mx, off);
+        if (lane >= off && s2 == sid) {
+            a.cnt += (int64_t)c2;
+            a.sum += (uint64_t)u2;
+            a.mn = (int64_t)n2 < a.mn ? (int64_t)n2 : a.mn;
+            a.mx = (int64_t)x2 > a.mx ? (int64_t)x2 : a.mx;
+        }
+    }
+    long long snext = __shfl_down(sid, 1);
+    bool lastg = (lane == 63) || (snext != sid);
+    if (have && (cnt != 0 || lastg)) {
+        atomicAdd((unsigned long long *)(out_count + segid), (unsigned long long)a.cnt);
+        atomicAdd((unsigned long long *)(out_sum + segid), (unsigned long long)a.sum);
+        atomicMin((long long *)(out_min + segid), (long long)a.mn);
+        atomicMax((long long *)(out_max + segid), (long long)a.mx);
+    }
+}
+
+hipError_t seg_stats(hipStream_t s, const uint64_t *k, const uint64_t *v, uint64_t n,
+                     int64_t *out_k, int64_t *out_count, int64_t *out_sum,
+                     int64_t *out_min, int64_t *out_max, uint64_t *h_nout, Ws &ws,
+                     bool packed) {
+    if (n == 0) { *h_nout = 0; return hipSuccess; }
+    if (n >= (1ULL << 32)) return hipErrorNotSupported; /* u32 head scan limit */
+    uint32_t nb = nblocks_for(n);
+    uint32_t *hc = (uint32_t *)ws.take(((size_t)nb + 1) * 4);
+    if (!hc) return hipErrorOutOfMemory;
+    {
+        ProfScope ps("head_count", s);
+        if (packed)
+            hipLaunchKernelGGL((k_head_count<true>), dim3(nb), dim3(BLOCK), 0, s, k, n, hc);
+        else
+            hipLaunchKernelGGL((k_head_count<false>), dim3(nb), dim3(BLOCK), 0, s, k, n, hc);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipMemsetAsync(hc + nb, 0, 4, s));
+    {
+        Ws w2 = ws;
+        HIP_TRY(scan_u32_excl(s, hc, (uint64_t)nb + 1, w2));
+    }
+    uint32_t total = 0;
+    HIP_TRY(hipMemcpyAsync(&total, hc + nb, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+
+    /* init the four accumulator columns, `total` rows each */
+    HIP_TRY(hipMemsetAsync(out_count, 0, (size_t)total * 8, s));
+    HIP_TRY(hipMemsetAsync(out_sum, 0, (size_t)total * 8, s));
+    hipLaunchKernelGGL(k_fill_i64, dim3(2048), dim3(BLOCK), 0, s, out_min, (uint64_t)total,
+                       INT64_MAX);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_fill_i64, dim3(2048), dim3(BLOCK), 0, s, out_max, (uint64_t)total,
+                       INT64_MIN);
+    HIP_TRY(hipGetLastError());
+    {
+        ProfScope ps("seg_stats", s);
+        if (packed)
+            hipLaunchKernelGGL((k_seg_stats<true>), dim3(nb), dim3(SEG_B), 0, s, k, v, n, hc,
+                               out_k, out_count, out_sum, out_min, out_max);
+        else
+            hipLaunchKernelGGL((k_seg_stats<false>), dim3(nb), dim3(SEG_B), 0, s, k, v, n, hc,
+                               out_k, out_count, out_sum, out_min, out_max);
+        HIP_TRY(hipGetLastError());
+    }
+    *h_nout = total;
+    return hipSuccess;
+}
+
+/* grouping sort (the arguments group_sort_reduce uses: relaxed order
+ * contract, packed rows kept) + the fused segmented pass */
+hipError_t group_sort_stats(hipStream_t s, const uint64_t *in_k, const uint64_t *in_v,
+                            uint64_t n, int64_t *out_k, int64_t *out_count,
+                            int64_t *out_sum, int64_t *out_min, int64_t *out_max,
+                            uint64_t *h_nout, Ws &ws) {
+    if (n == 0) { *h_nout = 0; return hipSuccess; }
+    const uint64_t *sk, *sv;
+    int pk = 0;
+    hipError_t e = group_sort_u64(s, in_k, in_v, n, 0, nullptr, 1, &pk, ws, &sk, &sv);
+    if (e != hipSuccess) return e;
+    return seg_stats(s, sk, sv, n, out_k, out_count, out_sum, out_min, out_max, h_nout, ws,
+                     pk != 0);
+}
+
+/* ------------------------------------------------------------------ */
 /* hash partition (map-side K1)                                        */
 
 __global__ void k_gather_starts(const uint32_t *bh_scanned, uint32_t nblocks,

@@ -24,6 +24,11 @@ OP_SUM_F64 = 2
 OP_MIN_I64 = 3
 OP_MAX_I64 = 4
 
+STAT_COUNT = 0
+STAT_SUM = 1
+STAT_MIN = 2
+STAT_MAX = 3
+
 MAP_VALUES_ADD = 0
 MAP_VALUES_MUL = 1
 MAP_KEYS_ADD = 2
@@ -76,7 +81,9 @@ def _check(rc, what, ctx=None):
         extra = b""
         if ctx is not None:
             extra = lib().vega_gpu_last_error(ctx)
-        raise VegaGpuError(f"{what} failed rc={rc} {extra!r}")
+        err = VegaGpuError(f"{what} failed rc={rc} {extra!r}")
+        err.rc = rc  # the VEGA_ERR_* code
+        raise err
 
 
 class VegaContext:
@@ -152,6 +159,15 @@ class Rdd:
                "reduce_by_key", self.ctx._c)
         return Rdd(self.ctx, out.value,
                    np.float64 if op == OP_SUM_F64 else np.int64)
+
+    def stats_by_key(self, nparts=256):
+        """combine_by_key (pair_rdd.rs:20-33) with C = (count, sum, min, max)
+        over i64 values, all four columns from one grouping sort"""
+        out = ctypes.c_uint64()
+        _check(lib().vega_gpu_stats_by_key(self.ctx._c, ctypes.c_uint64(self.h),
+                                           ctypes.c_uint32(nparts), ctypes.byref(out)),
+               "stats_by_key", self.ctx._c)
+        return StatsRdd(self.ctx, out.value)
 
     def map(self, op, p0=0):
         out = ctypes.c_uint64()
@@ -393,6 +409,45 @@ class Rdd:
         lib().vega_gpu_free_rdd(self.ctx._c, ctypes.c_uint64(self.h))
 
 
+class StatsRdd:
+    """result of Rdd.stats_by_key: per key (count, sum, min, max)"""
+
+    def __init__(self, ctx, handle):
+        self.ctx = ctx
+        self.h = handle
+
+    def count(self):
+        """number of keys"""
+        n = ctypes.c_uint64()
+        _check(lib().vega_gpu_count(self.ctx._c, ctypes.c_uint64(self.h),
+                                    ctypes.byref(n)), "count", self.ctx._c)
+        return n.value
+
+    def collect(self):
+        """(keys, count, sum, min, max) as int64 arrays, rows aligned"""
+        n = ctypes.c_uint64(0)
+        _check(lib().vega_gpu_collect_stats(self.ctx._c, ctypes.c_uint64(self.h),
+                                            None, None, None, None, None,
+                                            ctypes.byref(n)),
+               "collect_stats size", self.ctx._c)
+        cols = [np.empty(n.value, dtype=np.int64) for _ in range(5)]
+        _check(lib().vega_gpu_collect_stats(self.ctx._c, ctypes.c_uint64(self.h),
+                                            *[_pp(a) for a in cols], ctypes.byref(n)),
+               "collect_stats", self.ctx._c)
+        return tuple(a[:n.value] for a in cols)
+
+    def column(self, which):
+        """map_values(|c| c.<which>): a plain (key, column) Rdd (device copy)"""
+        out = ctypes.c_uint64()
+        _check(lib().vega_gpu_stats_column(self.ctx._c, ctypes.c_uint64(self.h),
+                                           ctypes.c_int(which), ctypes.byref(out)),
+               "stats_column", self.ctx._c)
+        return Rdd(self.ctx, out.value, np.int64)
+
+    def free(self):
+        lib().vega_gpu_free_rdd(self.ctx._c, ctypes.c_uint64(self.h))
+
+
 # ---------------- device-pointer API over torch tensors ----------------
 
 def _t(t):
@@ -462,6 +517,20 @@ def dev_sort_reduce(keys_t, vals_t, op, out_k, out_v, ws_t):
                                       _t(out_k), _t(out_v), ctypes.byref(nout),
                                       _t(ws_t), ctypes.c_size_t(ws_t.numel())),
            "dev_sort_reduce")
+    return nout.value
+
+
+def dev_sort_stats(keys_t, vals_t, out_k, out_count, out_sum, out_min, out_max, ws_t):
+    """grouping sort + fused (count, sum, min, max) per key; the five out
+    tensors hold n rows each; returns the number of keys"""
+    n = keys_t.numel()
+    nout = ctypes.c_uint64()
+    _check(lib().vega_dev_sort_stats_i64(_stream(), _t(keys_t), _t(vals_t),
+                                         ctypes.c_uint64(n), _t(out_k), _t(out_count),
+                                         _t(out_sum), _t(out_min), _t(out_max),
+                                         ctypes.byref(nout),
+                                         _t(ws_t), ctypes.c_size_t(ws_t.numel())),
+           "dev_sort_stats")
     return nout.value
 
 

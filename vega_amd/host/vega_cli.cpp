@@ -175,6 +175,21 @@ int main(int argc, char **argv) {
                          .reduce_by_key(VEGA_OP_SUM_I64, 1);
             CHECK_EQ(r.collect(), (pairs_t{{0, 10}}), "reduce(+)==10 golden");
         }
+        /* stats_by_key: combine_by_key with C = (count, sum, min, max);
+         * expected rows written out by hand */
+        {
+            pairs_t in{{7, 5}, {3, -2}, {7, -9}, {3, 4}, {7, 1}, {11, 0}, {3, 4}, {-1, 100}};
+            auto st = sc.make_rdd(in, 3).stats_by_key(3);
+            auto got = st.collect();
+            std::sort(got.begin(), got.end());
+            std::vector<vega::KeyStats> exp{
+                {-1, 1, 100, 100, 100}, {3, 3, 6, -2, 4}, {7, 3, -3, -9, 5}, {11, 1, 0, 0, 0}};
+            CHECK_EQ(got, exp, "stats_by_key hand-written (count, sum, min, max)");
+            CHECK_EQ(st.count(), (uint64_t)4, "stats_by_key count == #keys");
+            auto mx = st.column(VEGA_STAT_MAX);
+            CHECK_EQ(sorted(mx.collect()), (pairs_t{{-1, 100}, {3, 4}, {7, 5}, {11, 0}}),
+                     "stats_column(MAX) is a plain pair rdd");
+        }
         /* randomized reduce vs in-binary std::map (datagen formula inline) */
         {
             const uint64_t n = 250000, seed = 4242;

@@ -38,6 +38,55 @@ inline void check(int rc, const char *what, vega_ctx_t *c = nullptr) {
 
 class Context;
 
+class PairRdd;
+
+/* one row of stats_by_key: the key and its combiner C = (count, sum, min, max) */
+struct KeyStats {
+    int64_t key, count, sum, min, max;
+    bool operator==(const KeyStats &o) const {
+        return key == o.key && count == o.count && sum == o.sum && min == o.min && max == o.max;
+    }
+    bool operator<(const KeyStats &o) const { return key < o.key; }
+};
+
+/* Rdd<(i64, (count, sum, min, max))> — the result of PairRdd::stats_by_key */
+class StatsRdd {
+  public:
+    StatsRdd() = default;
+    StatsRdd(vega_ctx_t *c, vega_rdd_t h) : c_(c), h_(h) {}
+
+    /* number of keys */
+    uint64_t count() const {
+        uint64_t n = 0;
+        check(vega_gpu_count(c_, h_, &n), "count", c_);
+        return n;
+    }
+    /* rows in grouping order (unspecified, as for reduce_by_key) */
+    std::vector<KeyStats> collect() const {
+        uint64_t n = 0;
+        check(vega_gpu_collect_stats(c_, h_, nullptr, nullptr, nullptr, nullptr, nullptr, &n),
+              "collect_stats size", c_);
+        std::vector<int64_t> k(n), cnt(n), sum(n), mn(n), mx(n);
+        if (n)
+            check(vega_gpu_collect_stats(c_, h_, k.data(), cnt.data(), sum.data(), mn.data(),
+                                         mx.data(), &n), "collect_stats", c_);
+        std::vector<KeyStats> out(n);
+        for (uint64_t i = 0; i < n; i++) out[i] = {k[i], cnt[i], sum[i], mn[i], mx[i]};
+        return out;
+    }
+    /* map_values(|c| c.<which>): a plain pair rdd (defined below PairRdd) */
+    inline PairRdd column(vega_stat_t which) const;
+    void free() {
+        if (c_ && h_) vega_gpu_free_rdd(c_, h_);
+        h_ = 0;
+    }
+    vega_rdd_t handle() const { return h_; }
+
+  private:
+    vega_ctx_t *c_ = nullptr;
+    vega_rdd_t h_ = 0;
+};
+
 /* Rdd<(i64, i64|f64)> — handle + the PairRdd method surface */
 class PairRdd {
   public:
@@ -49,6 +98,12 @@ class PairRdd {
         vega_rdd_t out = 0;
         check(vega_gpu_reduce_by_key(c_, h_, op, num_splits, &out), "reduce_by_key", c_);
         return PairRdd(c_, out, op == VEGA_OP_SUM_F64);
+    }
+    /* pair_rdd.rs:20-33 combine_by_key with C = (count, sum, min, max) */
+    StatsRdd stats_by_key(uint32_t num_splits = 256) const {
+        vega_rdd_t out = 0;
+        check(vega_gpu_stats_by_key(c_, h_, num_splits, &out), "stats_by_key", c_);
+        return StatsRdd(c_, out);
     }
     /* pair_rdd.rs:35-52; group sizes (full groups: sort_by_key + scan host-side) */
     PairRdd group_by_key_count(uint32_t num_splits = 256) const {
@@ -198,6 +253,12 @@ class PairRdd {
     vega_rdd_t h_ = 0;
     bool f64_ = false;
 };
+
+inline PairRdd StatsRdd::column(vega_stat_t which) const {
+    vega_rdd_t out = 0;
+    check(vega_gpu_stats_column(c_, h_, which, &out), "stats_column", c_);
+    return PairRdd(c_, out, false);
+}
 
 /* Context::new (context.rs:147-164); local mode, one GPU per process */
 class Context {
