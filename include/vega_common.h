@@ -54,4 +54,57 @@ VEGA_INLINE VEGA_HD uint64_t vega_slice_start(uint64_t n, uint32_t nparts, uint3
     return ((__uint128_t)p * n) / nparts;
 }
 
+/* ---- sampling (sample / random_split / take_sample; DESIGN.md "Sampling") ----
+ * The reference seeds a Pcg64 per partition (utils/random.rs:59-234), so its
+ * row-level choices are unpinned. Here every decision about row i is a pure
+ * function of (seed, GLOBAL row index i): independent of nparts, of the grid
+ * and of how a launcher shards the rows. Decisions compare a 53-bit integer
+ * draw against integer thresholds the HOST derives from the probabilities —
+ * no floating point takes part in a keep/drop decision on the device. */
+#define VEGA_SAMPLE_ONE (1ULL << 53)   /* T(1): every draw is below it */
+#define VEGA_SAMPLE_TABLE_MAX 256      /* Poisson table cap (L <= 255) */
+#define VEGA_SAMPLE_LAMBDA_MAX 16.0    /* with-replacement fraction limit */
+#define VEGA_SPLIT_MAX 256             /* random_split weights limit */
+
+/* the 53-bit draw d_i of row i */
+VEGA_INLINE VEGA_HD uint64_t vega_sample_draw(uint64_t seed, uint64_t i) {
+    return vega_rand_u64(vega_hash_u64(seed), i) >> 11;
+}
+/* the same with hseed = vega_hash_u64(seed) hoisted (kernels get it as an argument) */
+VEGA_INLINE VEGA_HD uint64_t vega_sample_draw_h(uint64_t hseed, uint64_t i) {
+    return vega_rand_u64(hseed, i) >> 11;
+}
+/* and with the counter premultiplied: gx = VEGA_SAMPLE_STEP * (i + 1) mod 2^64
+ * (the multiplier inside vega_rand_u64), so a kernel walking rows at a fixed
+ * stride steps gx by one addition instead of a 64-bit multiply per row */
+#define VEGA_SAMPLE_STEP 0x9E3779B97F4A7C15ULL
+VEGA_INLINE VEGA_HD uint64_t vega_sample_draw_x(uint64_t hseed, uint64_t gx) {
+    return vega_hash_u64(hseed ^ gx) >> 11;
+}
+/* T(p) = min((uint64_t)(p * 2^53), 2^53), 0 for p <= 0 (and for NaN). Host side. */
+VEGA_INLINE VEGA_HD uint64_t vega_sample_threshold(double p) {
+    if (!(p > 0.0)) return 0;
+    double x = p * 9007199254740992.0;
+    if (x >= 9007199254740992.0) return VEGA_SAMPLE_ONE;
+    return (uint64_t)x;
+}
+/* Poisson copies of a row: c = #{ c < len : d >= thr[c] } (thr ascending) */
+VEGA_INLINE VEGA_HD uint32_t vega_sample_poisson_count(uint64_t d, const uint64_t *thr,
+                                                       uint32_t len) {
+    uint32_t c = 0;
+    while (c < len && d >= thr[c]) ++c;
+    return c;
+}
+/* random_split cell: #{ 1 <= j < nw : d >= bounds[j] }; bounds[0..nw] ascending,
+ * bounds[0] = 0 and bounds[nw] = 2^53 are never compared */
+VEGA_INLINE VEGA_HD uint32_t vega_sample_split_cell(uint64_t d, const uint64_t *bounds,
+                                                    uint32_t nw) {
+    uint32_t lo = 0, hi = nw - 1; /* answer in [0, nw-1] */
+    while (lo < hi) {
+        uint32_t m = (lo + hi + 1) >> 1;
+        if (d >= bounds[m]) lo = m; else hi = m - 1;
+    }
+    return lo;
+}
+
 #endif /* VEGA_COMMON_H */

@@ -234,6 +234,52 @@ int vega_gpu_take_ordered(vega_ctx_t *ctx, vega_rdd_t rdd, uint64_t num, int64_t
                           int64_t *vals, uint64_t *n_out);
 int vega_gpu_top(vega_ctx_t *ctx, vega_rdd_t rdd, uint64_t num, int64_t *keys,
                  int64_t *vals, uint64_t *n_out);
+/* ---- samplers (rdd.rs:623-783; samplers utils/random.rs:59-234) ----
+ * Whether row i is kept is a function of (seed, GLOBAL row index i) only:
+ * d_i = vega_sample_draw(seed, i), a 53-bit integer compared against integer
+ * thresholds T(p) = min((uint64_t)(p * 2^53), 2^53) that the host computes
+ * (vega_common.h; DESIGN.md "Sampling"). The result does not depend on
+ * nparts, the grid or the sharding, and differs row by row from the
+ * reference, whose per-partition Pcg64 stream is unpinned. Plain pair handles
+ * only (grouped / join-result / stats handles: VEGA_ERR_INVALID; ngpus > 1
+ * context: VEGA_ERR_UNSUPPORTED; n >= 2^32: VEGA_ERR_UNSUPPORTED). The input
+ * is never modified. i64 and f64 values both work (8 opaque bytes); results
+ * keep the source's value type and nparts. */
+/* sample (rdd.rs:690-702). with_replacement == 0: Bernoulli, keep row i iff
+ * d_i < T(fraction); fraction in [-1e-6, 1 + 1e-6], clamped to [0, 1], else
+ * (or NaN) VEGA_ERR_INVALID; row order kept. with_replacement != 0: Poisson
+ * with mean fraction, row i emitted c_i times in place (copies adjacent, row
+ * order kept), c_i read off the table of vega_sample_poisson_table; fraction
+ * < 0 or NaN: VEGA_ERR_INVALID, fraction > 16: VEGA_ERR_UNSUPPORTED. A result
+ * of 2^32 rows or more: VEGA_ERR_UNSUPPORTED. The result is allocated after
+ * the count is known (exact size). */
+int vega_gpu_sample(vega_ctx_t *ctx, vega_rdd_t rdd, int with_replacement, double fraction,
+                    uint64_t seed, vega_rdd_t *out);
+/* random_split (rdd.rs:623-672): outs[nw] independent handles, each freed on
+ * its own; on any failure none is left allocated. Bounds b_j = running sum of
+ * w_j / sum(w); row i goes to split #{ 1 <= j < nw : d_i >= T(b_j) }. The
+ * last bound is exactly 2^53: the splits are disjoint, their union is the
+ * input, each keeps row order. Split 0 equals sample(0, w_0 / sum(w), seed).
+ * A negative or NaN weight, sum(w) <= 0, nw == 0 or nw > 256:
+ * VEGA_ERR_INVALID. */
+int vega_gpu_random_split(vega_ctx_t *ctx, vega_rdd_t rdd, const double *weights, uint32_t nw,
+                          uint64_t seed, vega_rdd_t *outs);
+/* take_sample (rdd.rs:717-783): min(num, candidates) rows to the HOST arrays
+ * keys/vals (num rows each). num == 0 or an empty rdd: 0 rows. Candidates are
+ * all rows (without replacement, num >= n) or sample(with_replacement, f,
+ * seed + t) for attempts t = 0, 1, ... until it holds num rows, f from
+ * utils/random.rs:318-358 (100 failed attempts: VEGA_ERR_UNSUPPORTED, where
+ * the reference panics). Candidate j gets the priority
+ * vega_rand_u64(vega_hash_u64(~seed), j); the answer is the first rows of the
+ * candidates stably sorted by it. Extra memory is O(candidates). */
+int vega_gpu_take_sample(vega_ctx_t *ctx, vega_rdd_t rdd, int with_replacement, uint64_t num,
+                         uint64_t seed, int64_t *keys, void *vals, uint64_t *n_out);
+/* the Poisson table the kernels use for this fraction: thr[c] = T(cdf_c) for
+ * c < *len, with p_0 = exp(-f), p_c = p_{c-1} * f / c, cdf_c = cdf_{c-1} + p_c
+ * in IEEE doubles; *len = the first c with c > f and p_c < 2^-54 (at most
+ * 255). thr must hold 256 entries. Same argument errors as the sampler.
+ * Pure host code: needs no GPU and no context. */
+int vega_sample_poisson_table(double fraction, uint64_t *thr, int *len);
 int vega_gpu_free_rdd(vega_ctx_t *ctx, vega_rdd_t rdd);
 
 /* ---------------- profiling ---------------- */
@@ -353,6 +399,18 @@ int vega_dev_select_k_i64(void *stream, const int64_t *keys, const int64_t *vals
 int vega_dev_reduce_pairs(void *stream, const int64_t *keys, const void *vals, uint64_t n,
                           int op, int64_t *h_out_k, void *h_out_v, void *d_ws,
                           size_t ws_bytes);
+
+/* sample (as vega_gpu_sample) of n device rows whose first row has the GLOBAL
+ * index start, as in vega_dev_gen_uniform_i64: ranks that sample their own
+ * shards with their own start produce exactly the slices of the sample of the
+ * whole. vals / out_v are 8-byte values of either type. *h_nout = the rows
+ * the sample holds, also when that exceeds cap — then the call returns
+ * VEGA_ERR_CAP and writes nothing. d_ws: vega_dev_ws_bytes(n) suffices
+ * (VEGA_ERR_NOMEM if too small). Synchronizes the stream. */
+int vega_dev_sample(void *stream, const int64_t *keys, const void *vals, uint64_t n,
+                    int with_replacement, double fraction, uint64_t seed, uint64_t start,
+                    int64_t *out_k, void *out_v, uint64_t cap, uint64_t *h_nout,
+                    void *d_ws, size_t ws_bytes);
 
 #ifdef __cplusplus
 }

@@ -10,6 +10,7 @@
  */
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <map>
@@ -1260,6 +1261,255 @@ int vega_gpu_stats_column(vega_ctx_t *c, vega_rdd_t stats, vega_stat_t which, ve
     return VEGA_OK;
 }
 
+/* ---------------- samplers ---------------- */
+/* sample / random_split / take_sample (rdd.rs:623-783). Every keep/drop
+ * decision is a function of (seed, global row index) compared against integer
+ * thresholds computed HERE, on the host, in IEEE doubles (vega_common.h;
+ * DESIGN.md "Sampling"). Plain pair handles only; the input is never
+ * modified; results are allocated after the count is known. */
+
+/* The Poisson table the kernels use: thr[c] = T(cdf_c), c < *len. thr must
+ * hold VEGA_SAMPLE_TABLE_MAX entries. Pure host code. */
+int vega_sample_poisson_table(double fraction, uint64_t *thr, int *len) {
+    if (!thr || !len) return VEGA_ERR_INVALID;
+    *len = 0;
+    if (!(fraction >= 0.0)) return VEGA_ERR_INVALID; /* negative or NaN */
+    if (fraction > VEGA_SAMPLE_LAMBDA_MAX) return VEGA_ERR_UNSUPPORTED;
+    double p = exp(-fraction), cdf = p;
+    int c = 0;
+    for (;;) {
+        if (((double)c > fraction && p < 0x1p-54) || c == VEGA_SAMPLE_TABLE_MAX - 1) break;
+        thr[c] = vega_sample_threshold(cdf);
+        ++c;
+        p = p * fraction / (double)c;
+        cdf = cdf + p;
+    }
+    *len = c;
+    return VEGA_OK;
+}
+
+/* argument checks + thresholds shared by the handle and the pointer entry;
+ * err may be null */
+static int sample_spec(int with_replacement, double fraction, uint64_t seed, uint64_t start,
+                       SampleSpec *sp, char *err, size_t errlen) {
+    sp->repl = with_replacement != 0;
+    sp->hseed = vega_hash_u64(seed);
+    sp->start = start;
+    if (!sp->repl) {
+        if (!(fraction >= -1e-6 && fraction <= 1.0 + 1e-6)) return VEGA_ERR_INVALID;
+        sp->thr = vega_sample_threshold(fraction > 1.0 ? 1.0 : fraction);
+        return VEGA_OK;
+    }
+    int len = 0;
+    int rc = vega_sample_poisson_table(fraction, sp->tab, &len);
+    if (rc == VEGA_ERR_UNSUPPORTED && err)
+        snprintf(err, errlen, "sample: with-replacement fraction %g exceeds the supported %g",
+                 fraction, VEGA_SAMPLE_LAMBDA_MAX);
+    sp->len = (uint32_t)len;
+    return rc;
+}
+
+static int hip_rc(hipError_t e) {
+    if (e == hipSuccess) return VEGA_OK;
+    if (e == hipErrorNotSupported) return VEGA_ERR_UNSUPPORTED;
+    if (e == hipErrorInvalidValue) return VEGA_ERR_INVALID;
+    return e == hipErrorOutOfMemory ? VEGA_ERR_NOMEM : VEGA_ERR_HIP;
+}
+
+/* count step on a handle: *total = output rows; refuses >= 2^32 */
+static int sample_plan(vega_ctx *c, RddImpl *r, const SampleSpec &sp, Ws &ws, SamplePlan *pl,
+                       uint64_t *total) {
+    hipError_t e = sample_count(c->stream, r->n, sp, pl, total, ws);
+    if (e != hipSuccess) {
+        snprintf(c->err, sizeof c->err, "sample: %s", hipGetErrorString(e));
+        return hip_rc(e);
+    }
+    if (*total >= (1ULL << 32)) {
+        snprintf(c->err, sizeof c->err, "sample: %llu output rows exceed the 2^32-1 per-call limit",
+                 (unsigned long long)*total);
+        return VEGA_ERR_UNSUPPORTED;
+    }
+    return VEGA_OK;
+}
+
+int vega_gpu_sample(vega_ctx_t *c, vega_rdd_t rdd, int with_replacement, double fraction,
+                    uint64_t seed, vega_rdd_t *out) {
+    RddImpl *r;
+    int rc = action_rdd(c, rdd, &r);
+    if (rc) return rc;
+    if (!out) return VEGA_ERR_INVALID;
+    *out = 0;
+    SampleSpec sp;
+    rc = sample_spec(with_replacement, fraction, seed, 0, &sp, c->err, sizeof c->err);
+    if (rc) return rc;
+    rc = ensure_ws_bytes(c, sample_ws_bytes(r->n));
+    if (rc) return rc;
+    Ws ws(c->ws, c->ws_bytes);
+    SamplePlan pl;
+    uint64_t total = 0;
+    rc = sample_plan(c, r, sp, ws, &pl, &total);
+    if (rc) return rc;
+    RddImpl *o;
+    rc = new_rdd(c, total ? total : 1, r->vtype, r->nparts, &o, out);
+    if (rc == VEGA_OK && total) {
+        hipError_t e = sample_emit(c->stream, (const uint64_t *)r->d_k, (const uint64_t *)r->d_v,
+                                   r->n, sp, pl, (uint64_t *)o->d_k, (uint64_t *)o->d_v);
+        if (e != hipSuccess) {
+            snprintf(c->err, sizeof c->err, "sample: %s", hipGetErrorString(e));
+            rc = hip_rc(e);
+        }
+    }
+    if (rc) { /* no half-built handle is handed out */
+        if (*out) vega_gpu_free_rdd(c, *out);
+        *out = 0;
+        return rc;
+    }
+    o->n = total;
+    return VEGA_OK;
+}
+
+int vega_gpu_random_split(vega_ctx_t *c, vega_rdd_t rdd, const double *weights, uint32_t nw,
+                          uint64_t seed, vega_rdd_t *outs) {
+    RddImpl *r;
+    int rc = action_rdd(c, rdd, &r);
+    if (rc) return rc;
+    if (!weights || !outs || nw == 0 || nw > VEGA_SPLIT_MAX) return VEGA_ERR_INVALID;
+    for (uint32_t j = 0; j < nw; ++j) outs[j] = 0;
+    double sum = 0.0;
+    for (uint32_t j = 0; j < nw; ++j) {
+        if (!(weights[j] >= 0.0)) return VEGA_ERR_INVALID; /* negative or NaN */
+        sum += weights[j];
+    }
+    if (!(sum > 0.0) || sum > 1.7976931348623157e308) return VEGA_ERR_INVALID;
+    /* rdd.rs:643-651: running sum of w/sum; the last bound is exactly 2^53 so
+     * no row is lost to float jitter */
+    uint64_t bounds[VEGA_SPLIT_MAX + 1];
+    double run = 0.0;
+    bounds[0] = 0;
+    for (uint32_t j = 1; j < nw; ++j) {
+        run = run + weights[j - 1] / sum;
+        bounds[j] = vega_sample_threshold(run);
+    }
+    bounds[nw] = VEGA_SAMPLE_ONE;
+    rc = ensure_ws_bytes(c, split_ws_bytes(r->n, nw));
+    if (rc) return rc;
+    Ws ws(c->ws, c->ws_bytes);
+    const uint64_t hseed = vega_hash_u64(seed);
+    SplitPlan pl;
+    uint64_t counts[VEGA_SPLIT_MAX];
+    hipError_t e = split_count(c->stream, r->n, 0, hseed, bounds, nw, &pl, counts, ws);
+    uint64_t *pk[VEGA_SPLIT_MAX], *pv[VEGA_SPLIT_MAX];
+    rc = hip_rc(e);
+    for (uint32_t j = 0; j < nw && rc == VEGA_OK; ++j) {
+        RddImpl *o;
+        rc = new_rdd(c, counts[j] ? counts[j] : 1, r->vtype, r->nparts, &o, &outs[j]);
+        if (rc) break;
+        o->n = counts[j];
+        pk[j] = (uint64_t *)o->d_k;
+        pv[j] = (uint64_t *)o->d_v;
+    }
+    if (rc == VEGA_OK) {
+        e = split_scatter(c->stream, (const uint64_t *)r->d_k, (const uint64_t *)r->d_v, r->n, 0,
+                          hseed, nw, pl, pk, pv);
+        rc = hip_rc(e);
+    }
+    if (rc) { /* on any failure none is left allocated */
+        if (e != hipSuccess)
+            snprintf(c->err, sizeof c->err, "random_split: %s", hipGetErrorString(e));
+        for (uint32_t j = 0; j < nw; ++j) {
+            if (outs[j]) vega_gpu_free_rdd(c, outs[j]);
+            outs[j] = 0;
+        }
+    }
+    return rc;
+}
+
+/* utils/random.rs:318-358 compute_fraction_for_sample_size */
+static double fraction_for_sample_size(uint64_t num, uint64_t total, bool with_replacement) {
+    if (with_replacement) {
+        double s = (double)num;
+        double k = s < 6.0 ? 12.0 : (s < 16.0 ? 9.0 : 6.0);
+        double ub = s + k * sqrt(s);
+        return (ub > 1e-10 ? ub : 1e-10) / (double)total;
+    }
+    double f = (double)num / (double)total;
+    double gamma = -log(1e-4) / (double)total;
+    double m = f + gamma + sqrt(gamma * gamma + 2.0 * gamma * f);
+    if (m < 1e-10) m = 1e-10;
+    return m < 1.0 ? m : 1.0;
+}
+
+int vega_gpu_take_sample(vega_ctx_t *c, vega_rdd_t rdd, int with_replacement, uint64_t num,
+                         uint64_t seed, int64_t *keys, void *vals, uint64_t *n_out) {
+    RddImpl *r;
+    int rc = action_rdd(c, rdd, &r);
+    if (rc) return rc;
+    if (!n_out) return VEGA_ERR_INVALID;
+    *n_out = 0;
+    if (num == 0 || r->n == 0) return VEGA_OK; /* rdd.rs:732-739 */
+    if (!keys || !vals) return VEGA_ERR_INVALID;
+    const bool repl = with_replacement != 0;
+    /* candidates: all rows, or an oversampled sample(…, seed + attempt) */
+    const uint64_t *ck = (const uint64_t *)r->d_k, *cv = (const uint64_t *)r->d_v;
+    uint64_t m = r->n;
+    uint64_t *bufs[4] = {nullptr, nullptr, nullptr, nullptr}; /* cand k/v, out k/v */
+    hipError_t e = hipSuccess;
+    do {
+        if (repl || num < r->n) {
+            const double fraction = fraction_for_sample_size(num, r->n, repl);
+            rc = ensure_ws_bytes(c, sample_ws_bytes(r->n));
+            if (rc) break;
+            SampleSpec sp;
+            SamplePlan pl;
+            bool enough = false;
+            for (uint64_t attempt = 0; attempt < 100 && !enough; ++attempt) {
+                rc = sample_spec(repl, fraction, seed + attempt, 0, &sp, c->err, sizeof c->err);
+                if (rc) break;
+                Ws ws(c->ws, c->ws_bytes);
+                rc = sample_plan(c, r, sp, ws, &pl, &m);
+                if (rc) break;
+                enough = m >= num;
+            }
+            if (rc) break;
+            if (!enough) { /* the reference panics here (rdd.rs:776-778) */
+                snprintf(c->err, sizeof c->err,
+                         "take_sample: repeated sampling 100 times; aborting");
+                rc = VEGA_ERR_UNSUPPORTED;
+                break;
+            }
+            if ((e = hipMalloc(&bufs[0], m * 8)) != hipSuccess) break;
+            if ((e = hipMalloc(&bufs[1], m * 8)) != hipSuccess) break;
+            /* the plan of the last (sufficient) attempt is still in the workspace */
+            if ((e = sample_emit(c->stream, ck, cv, r->n, sp, pl, bufs[0], bufs[1])) != hipSuccess)
+                break;
+            /* the ranking below may regrow the workspace the plan lives in */
+            if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) break;
+            ck = bufs[0];
+            cv = bufs[1];
+        }
+        const uint64_t take = num < m ? num : m;
+        rc = ensure_ws_bytes(c, sample_rank_ws_bytes(m));
+        if (rc) break;
+        if ((e = hipMalloc(&bufs[2], take * 8)) != hipSuccess) break;
+        if ((e = hipMalloc(&bufs[3], take * 8)) != hipSuccess) break;
+        Ws ws(c->ws, c->ws_bytes);
+        if ((e = sample_rank_gather(c->stream, ck, cv, m, take, vega_hash_u64(~seed), bufs[2],
+                                    bufs[3], ws)) != hipSuccess) break;
+        if ((e = hipMemcpyAsync(keys, bufs[2], take * 8, hipMemcpyDeviceToHost, c->stream)) != hipSuccess) break;
+        if ((e = hipMemcpyAsync(vals, bufs[3], take * 8, hipMemcpyDeviceToHost, c->stream)) != hipSuccess) break;
+        if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) break;
+        *n_out = take;
+    } while (0);
+    if (e != hipSuccess) {
+        snprintf(c->err, sizeof c->err, "take_sample: %s", hipGetErrorString(e));
+        rc = hip_rc(e);
+    }
+    (void)hipStreamSynchronize(c->stream);
+    for (uint64_t *b : bufs)
+        if (b) (void)hipFree(b);
+    return rc;
+}
+
 int vega_gpu_free_rdd(vega_ctx_t *c, vega_rdd_t rdd) {
     auto it = c->rdds.find(rdd);
     if (it == c->rdds.end()) return VEGA_ERR_INVALID;
@@ -1450,6 +1700,38 @@ int vega_dev_reduce_pairs(void *stream, const int64_t *keys, const void *vals, u
     hipError_t e = col_reduce((hipStream_t)stream, keys, vals, n, op, h_out_k, h_out_v, ws);
     if (e == hipErrorNotSupported) return VEGA_ERR_UNSUPPORTED;
     return e == hipSuccess ? VEGA_OK : (e == hipErrorOutOfMemory ? VEGA_ERR_CAP : VEGA_ERR_HIP);
+}
+
+/* sample on device buffers (see vega_gpu.h). The count pass always runs, so
+ * *h_nout is the needed row count even when it exceeds cap; the emit pass is
+ * launched only when everything fits. Synchronizes the stream. */
+int vega_dev_sample(void *stream, const int64_t *keys, const void *vals, uint64_t n,
+                    int with_replacement, double fraction, uint64_t seed, uint64_t start,
+                    int64_t *out_k, void *out_v, uint64_t cap, uint64_t *h_nout,
+                    void *d_ws, size_t ws_bytes) {
+    if (!h_nout) return VEGA_ERR_INVALID;
+    *h_nout = 0;
+    SampleSpec sp;
+    int rc = sample_spec(with_replacement, fraction, seed, start, &sp, nullptr, 0);
+    if (rc) return rc;
+    if (n >= (1ULL << 32)) return VEGA_ERR_UNSUPPORTED;
+    if (!n) return VEGA_OK;
+    if (!keys || !vals) return VEGA_ERR_INVALID;
+    if (!d_ws || ws_bytes < sample_ws_bytes(n)) return VEGA_ERR_NOMEM;
+    Ws ws(d_ws, ws_bytes);
+    SamplePlan pl;
+    uint64_t total = 0;
+    hipError_t e = sample_count((hipStream_t)stream, n, sp, &pl, &total, ws);
+    if (e != hipSuccess) return hip_rc(e);
+    *h_nout = total;
+    if (total >= (1ULL << 32)) return VEGA_ERR_UNSUPPORTED;
+    if (total > cap) return VEGA_ERR_CAP; /* nothing is written */
+    if (!total) return VEGA_OK;
+    if (!out_k || !out_v) return VEGA_ERR_INVALID;
+    e = sample_emit((hipStream_t)stream, (const uint64_t *)keys, (const uint64_t *)vals, n, sp,
+                    pl, (uint64_t *)out_k, (uint64_t *)out_v);
+    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+    return hip_rc(e);
 }
 
 /* diagnostic (VEGA_PHASE_PROF=1 builds/runs): per-phase shader-cycle sums of

@@ -176,6 +176,59 @@ hipError_t select_k(hipStream_t s, const int64_t *keys, const int64_t *vals, uin
                     int64_t *out_k, int64_t *out_v, uint64_t *h_nout, int *h_passes,
                     Ws &ws, const char **err);
 
+/* ---- samplers (rdd.rs:623-783 sample / random_split / take_sample) ----
+ * Decisions are functions of (seed, global row index) only — vega_common.h.
+ * Each op is a count step (no row data read; host learns the sizes, the
+ * caller allocates exactly) and an emit step over the same plan. */
+
+struct SampleSpec {
+    int repl = 0;          /* 0 Bernoulli (thr), 1 Poisson (tab/len) */
+    uint64_t hseed = 0;    /* vega_hash_u64(seed) */
+    uint64_t start = 0;    /* global index of row 0 */
+    uint64_t thr = 0;      /* Bernoulli: keep iff draw < thr */
+    uint32_t len = 0;      /* Poisson table length, 1..VEGA_SAMPLE_TABLE_MAX */
+    uint64_t tab[256];     /* Poisson thresholds, ascending */
+};
+struct SamplePlan { /* device scratch carved from the Ws by sample_count */
+    uint32_t *bc = nullptr;   /* scanned per-tile output bases */
+    uint64_t *tab = nullptr;
+};
+size_t sample_ws_bytes(uint64_t n);
+/* kernel k_sample_count + scan. *h_total = output rows (u64, after a stream
+ * sync). A total >= 2^32 leaves the plan empty: the caller must refuse. */
+hipError_t sample_count(hipStream_t s, uint64_t n, const SampleSpec &sp, SamplePlan *pl,
+                        uint64_t *h_total, Ws &ws);
+/* kernel k_sample_emit: out_* hold *h_total rows; row order kept, Poisson
+ * copies adjacent. Values are 8 opaque bytes. Async on s. */
+hipError_t sample_emit(hipStream_t s, const uint64_t *in_k, const uint64_t *in_v, uint64_t n,
+                       const SampleSpec &sp, const SamplePlan &pl, uint64_t *out_k,
+                       uint64_t *out_v);
+
+struct SplitPlan {
+    uint32_t *bh = nullptr, *starts = nullptr;
+    uint64_t *bounds = nullptr;
+    uint64_t **ptr_k = nullptr, **ptr_v = nullptr;
+};
+size_t split_ws_bytes(uint64_t n, uint32_t nw);
+/* h_bounds: nw+1 ascending integer bounds (bounds[0] = 0, bounds[nw] = 2^53);
+ * h_counts[nw] = rows per split (after a stream sync) */
+hipError_t split_count(hipStream_t s, uint64_t n, uint64_t start, uint64_t hseed,
+                       const uint64_t *h_bounds, uint32_t nw, SplitPlan *pl,
+                       uint64_t *h_counts, Ws &ws);
+/* stable scatter into nw separate (k, v) buffers (host arrays of device
+ * pointers, each holding its h_counts rows). Synchronizes s. */
+hipError_t split_scatter(hipStream_t s, const uint64_t *in_k, const uint64_t *in_v, uint64_t n,
+                         uint64_t start, uint64_t hseed, uint32_t nw, const SplitPlan &pl,
+                         uint64_t *const *h_out_k, uint64_t *const *h_out_v);
+
+/* take_sample's shuffle: priority vega_rand_u64(hseed, j) per candidate j,
+ * stable ascending sort, first num candidates gathered into out_* (device,
+ * num <= m rows). Memory O(m). Async on s. */
+size_t sample_rank_ws_bytes(uint64_t m);
+hipError_t sample_rank_gather(hipStream_t s, const uint64_t *cand_k, const uint64_t *cand_v,
+                              uint64_t m, uint64_t num, uint64_t hseed, uint64_t *out_k,
+                              uint64_t *out_v, Ws &ws);
+
 size_t ws_bytes_for(uint64_t n);
 
 /* diagnostic phase-cycle buffer (VEGA_PHASE_PROF=1|2), else nullptr */

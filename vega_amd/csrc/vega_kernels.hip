@@ -2216,6 +2216,425 @@ hipError_t narrow_filter(hipStream_t s, const int64_t *in_k, const int64_t *in_v
 }
 
 /* ------------------------------------------------------------------ */
+/* samplers (rdd.rs:623-702 sample / random_split; utils/random.rs:59-234)
+ *
+ * Whether row i is kept is a function of (seed, global index i) alone
+ * (vega_common.h), so the count pass reads no row data and the emit pass
+ * loads only the rows it keeps. Same count -> scan_u32_excl -> emit shape as
+ * narrow_filter. Tile layout is ROUND-MAJOR: in round j thread t owns row
+ * tbase + j*BLOCK + t, so the 64 rows a wave looks at in one round are
+ * adjacent — at small fractions the few kept loads of a round fall into the
+ * same 512 B instead of 64 scattered sectors, and the kept rows of a round
+ * are stored contiguously. Stable order is (round, wave, lane). */
+
+/* copies of row i: Bernoulli 0/1 against one threshold, Poisson via the table
+ * (staged in LDS by the caller) */
+/* gx = VEGA_SAMPLE_STEP * (global index + 1): the premultiplied counter of
+ * vega_sample_draw_x, stepped by VEGA_SAMPLE_STEP * BLOCK from round to round */
+template <bool REPL>
+__device__ __forceinline__ uint32_t sample_copies(uint64_t hseed, uint64_t gx, uint64_t thr,
+                                                  const uint64_t *tab, uint32_t len) {
+    uint64_t d = vega_sample_draw_x(hseed, gx);
+    if (!REPL) return d < thr ? 1u : 0u;
+    return vega_sample_poisson_count(d, tab, len);
+}
+
+/* one count per 4096-row tile + the u64 grand total; touches no row data.
+ * A bounded grid walks the tiles, so the total takes one atomic per BLOCK
+ * (a few thousand on one address), not one per tile. */
+template <bool REPL>
+__global__ __launch_bounds__(BLOCK) void k_sample_count(
+    uint64_t n, uint64_t start, uint64_t hseed, uint64_t thr, const uint64_t *tab_g,
+    uint32_t len, uint32_t ntiles, uint32_t *bc, unsigned long long *total) {
+    __shared__ uint32_t wsum[BLOCK / 64];
+    __shared__ uint64_t tab[VEGA_SAMPLE_TABLE_MAX];
+    if (REPL) {
+        for (uint32_t i = threadIdx.x; i < len; i += BLOCK) tab[i] = tab_g[i];
+        __syncthreads();
+    }
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    unsigned long long mine = 0; /* thread 0: this block's tiles */
+    for (uint32_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        uint64_t tbase = (uint64_t)tile * TILE;
+        uint64_t gx = VEGA_SAMPLE_STEP * (start + tbase + threadIdx.x + 1);
+        uint32_t c = 0;
+#pragma unroll
+        for (int j = 0; j < IPT; ++j) {
+            uint64_t idx = tbase + (uint64_t)j * BLOCK + threadIdx.x;
+            if (idx < n) c += sample_copies<REPL>(hseed, gx, thr, tab, len);
+            gx += VEGA_SAMPLE_STEP * BLOCK;
+        }
+        for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off);
+        if (lane == 0) wsum[w] = c;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            uint32_t t = 0;
+            for (int i = 0; i < BLOCK / 64; ++i) t += wsum[i];
+            bc[tile] = t;
+            mine += t;
+        }
+        __syncthreads(); /* wsum is rewritten by the next tile */
+    }
+    if (threadIdx.x == 0 && mine) atomicAdd(total, mine);
+}
+
+/* recomputes the draws (no flag array), loads only kept rows, writes each at
+ * base[tile] + its stable rank, c adjacent copies under REPL. Values are 8
+ * opaque bytes. */
+template <bool REPL>
+__global__ __launch_bounds__(BLOCK) void k_sample_emit(
+    const uint64_t *keys, const uint64_t *vals, uint64_t n, uint64_t start, uint64_t hseed,
+    uint64_t thr, const uint64_t *tab_g, uint32_t len, const uint32_t *base,
+    uint64_t *out_k, uint64_t *out_v) {
+    __shared__ uint32_t rw[IPT * (BLOCK / 64)]; /* (round, wave) totals -> exclusive offsets */
+    __shared__ uint64_t tab[VEGA_SAMPLE_TABLE_MAX];
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    if (REPL) {
+        for (uint32_t i = t; i < len; i += BLOCK) tab[i] = tab_g[i];
+        __syncthreads();
+    }
+    const uint64_t tbase = (uint64_t)blockIdx.x * TILE;
+    uint32_t cnt[IPT], before[IPT]; /* copies of my row / copies in lower lanes, per round */
+    uint64_t gx = VEGA_SAMPLE_STEP * (start + tbase + t + 1);
+#pragma unroll
+    for (int j = 0; j < IPT; ++j) {
+        uint64_t idx = tbase + (uint64_t)j * BLOCK + t;
+        uint32_t c = 0;
+        if (idx < n) c = sample_copies<REPL>(hseed, gx, thr, tab, len);
+        gx += VEGA_SAMPLE_STEP * BLOCK;
+        cnt[j] = c;
+        uint32_t tot;
+        if (!REPL) {
+            uint64_t m = __ballot(c != 0);
+            before[j] = (uint32_t)__popcll(m & (((uint64_t)1 << lane) - 1));
+            tot = (uint32_t)__popcll(m);
+        } else {
+            uint32_t inc = c;
+            for (int off = 1; off < 64; off <<= 1) {
+                uint32_t u = __shfl_up(inc, off);
+                if (lane >= off) inc += u;
+            }
+            before[j] = inc - c;
+            tot = __shfl(inc, 63);
+        }
+        if (lane == 0) rw[j * (BLOCK / 64) + w] = tot;
+    }
+    __syncthreads();
+    if (t < 64) { /* exclusive scan of the 64 (round, wave) totals by wave 0 */
+        uint32_t v = rw[t], inc = v;
+        for (int off = 1; off < 64; off <<= 1) {
+            uint32_t u = __shfl_up(inc, off);
+            if (lane >= off) inc += u;
+        }
+        rw[t] = inc - v;
+    }
+    __syncthreads();
+    const uint64_t b0 = base[blockIdx.x];
+#pragma unroll
+    for (int j = 0; j < IPT; ++j) {
+        if (cnt[j]) {
+            uint64_t idx = tbase + (uint64_t)j * BLOCK + t;
+            uint64_t k = keys[idx], v = vals[idx];
+            uint64_t pos = b0 + rw[j * (BLOCK / 64) + w] + before[j];
+            if (!REPL) {
+                out_k[pos] = k;
+                out_v[pos] = v;
+            } else {
+                for (uint32_t c = 0; c < cnt[j]; ++c) {
+                    out_k[pos + c] = k;
+                    out_v[pos + c] = v;
+                }
+            }
+        }
+    }
+}
+
+static_assert(IPT * (BLOCK / 64) == 64, "k_sample_emit scans its (round, wave) totals in one wave");
+
+size_t sample_ws_bytes(uint64_t n) {
+    size_t nb = nblocks_for(n ? n : 1);
+    size_t b = ((nb + 1) * 4 + 255) & ~(size_t)255;             /* tile counts + total slot */
+    b += ((nb / 2048 + 4096) * 4 + 255) & ~(size_t)255;         /* scan recursion partials */
+    b += VEGA_SAMPLE_TABLE_MAX * 8 + 256;                       /* Poisson table, u64 total */
+    return b + 4096;
+}
+
+hipError_t sample_count(hipStream_t s, uint64_t n, const SampleSpec &sp, SamplePlan *pl,
+                        uint64_t *h_total, Ws &ws) {
+    *h_total = 0;
+    pl->bc = nullptr;
+    pl->tab = nullptr;
+    if (n >= (1ULL << 32)) return hipErrorNotSupported; /* u32 tile counts / scan */
+    if (sp.repl && (sp.len == 0 || sp.len > VEGA_SAMPLE_TABLE_MAX)) return hipErrorInvalidValue;
+    if (n == 0) return hipSuccess;
+    uint32_t nb = nblocks_for(n);
+    uint32_t *bc = (uint32_t *)ws.take(((size_t)nb + 1) * 4);
+    uint64_t *tab = (uint64_t *)ws.take(VEGA_SAMPLE_TABLE_MAX * 8);
+    unsigned long long *tot = (unsigned long long *)ws.take(8);
+    if (!bc || !tab || !tot) return hipErrorOutOfMemory;
+    HIP_TRY(hipMemsetAsync(tot, 0, 8, s));
+    if (sp.repl)
+        HIP_TRY(hipMemcpyAsync(tab, sp.tab, (size_t)sp.len * 8, hipMemcpyHostToDevice, s));
+    {
+        ProfScope ps("sample_count", s);
+        uint32_t gb = nb < 2048 ? nb : 2048;
+        if (sp.repl)
+            hipLaunchKernelGGL(k_sample_count<true>, dim3(gb), dim3(BLOCK), 0, s, n, sp.start,
+                               sp.hseed, sp.thr, tab, sp.len, nb, bc, tot);
+        else
+            hipLaunchKernelGGL(k_sample_count<false>, dim3(gb), dim3(BLOCK), 0, s, n, sp.start,
+                               sp.hseed, sp.thr, tab, sp.len, nb, bc, tot);
+        HIP_TRY(hipGetLastError());
+    }
+    unsigned long long total = 0;
+    HIP_TRY(hipMemcpyAsync(&total, tot, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    *h_total = total;
+    if (total >= (1ULL << 32)) return hipSuccess; /* caller refuses; the u32 scan would wrap */
+    HIP_TRY(hipMemsetAsync(bc + nb, 0, 4, s));
+    {
+        Ws w2 = ws;
+        HIP_TRY(scan_u32_excl(s, bc, (uint64_t)nb + 1, w2));
+    }
+    pl->bc = bc;
+    pl->tab = tab;
+    return hipSuccess;
+}
+
+hipError_t sample_emit(hipStream_t s, const uint64_t *in_k, const uint64_t *in_v, uint64_t n,
+                       const SampleSpec &sp, const SamplePlan &pl, uint64_t *out_k,
+                       uint64_t *out_v) {
+    if (n == 0) return hipSuccess;
+    if (!pl.bc) return hipErrorInvalidValue;
+    uint32_t nb = nblocks_for(n);
+    ProfScope ps("sample_emit", s);
+    if (sp.repl)
+        hipLaunchKernelGGL(k_sample_emit<true>, dim3(nb), dim3(BLOCK), 0, s, in_k, in_v, n,
+                           sp.start, sp.hseed, sp.thr, pl.tab, sp.len, pl.bc, out_k, out_v);
+    else
+        hipLaunchKernelGGL(k_sample_emit<false>, dim3(nb), dim3(BLOCK), 0, s, in_k, in_v, n,
+                           sp.start, sp.hseed, sp.thr, pl.tab, sp.len, pl.bc, out_k, out_v);
+    return hipGetLastError();
+}
+
+/* ---- random_split: stable W-way scatter keyed on the ROW INDEX ----
+ * The digit functors of partition_generic see only the key; the cell of a row
+ * needs its global index, and the W results are separate allocations sized
+ * after the count. So this is the small sibling of k_block_hist / k_scatter:
+ * the same wave-synchronous ballot ranking over each wave's contiguous
+ * 1024-row chunk, but the cell comes from (seed, index), the count pass reads
+ * no row data, and rows go straight to their split's own buffer. */
+
+__device__ __forceinline__ uint32_t split_cell(uint64_t hseed, uint64_t gi,
+                                               const uint64_t *bounds, uint32_t nw) {
+    return vega_sample_split_cell(vega_sample_draw_h(hseed, gi), bounds, nw);
+}
+
+/* cell-major count matrix bh[cell][tile] for the device-wide scan */
+__global__ __launch_bounds__(BLOCK) void k_split_count(
+    uint64_t n, uint64_t start, uint64_t hseed, const uint64_t *bounds_g, uint32_t nw,
+    uint32_t nblocks, uint32_t *bh) {
+    __shared__ uint32_t h[VEGA_SPLIT_MAX];
+    __shared__ uint64_t bounds[VEGA_SPLIT_MAX + 1];
+    const int t = threadIdx.x, lane = t & 63;
+    h[t] = 0;
+    for (uint32_t i = t; i <= nw; i += BLOCK) bounds[i] = bounds_g[i];
+    __syncthreads();
+    const uint64_t tbase = (uint64_t)blockIdx.x * TILE;
+#pragma unroll 4
+    for (int j = 0; j < IPT; ++j) {
+        uint64_t idx = tbase + (uint64_t)j * BLOCK + t;
+        bool valid = idx < n;
+        uint32_t d = valid ? split_cell(hseed, start + idx, bounds, nw) : 0;
+        uint64_t m = wave_match8(d, valid);
+        int leader = (int)__ffsll((unsigned long long)m) - 1;
+        if (valid && lane == leader) atomicAdd(&h[d], (uint32_t)__popcll(m));
+    }
+    __syncthreads();
+    if ((uint32_t)t < nw) bh[(uint64_t)t * nblocks + blockIdx.x] = h[t];
+}
+
+static_assert(BLOCK == VEGA_SPLIT_MAX, "split kernels index their cell counters by thread");
+
+/* ranks (no data), then loads each row once and stores it at
+ * outs[cell] + (bh_scanned[cell][tile] - starts[cell]) + stable tile rank */
+__global__ __launch_bounds__(BLOCK) void k_split_scatter(
+    const uint64_t *in_k, const uint64_t *in_v, uint64_t n, uint64_t start, uint64_t hseed,
+    const uint64_t *bounds_g, uint32_t nw, uint32_t nblocks, const uint32_t *bh_scanned,
+    const uint32_t *starts, uint64_t *const *out_k, uint64_t *const *out_v) {
+    __shared__ uint32_t whist[(BLOCK / 64) * VEGA_SPLIT_MAX]; /* per-wave cell counters */
+    __shared__ uint64_t bounds[VEGA_SPLIT_MAX + 1];
+    __shared__ uint32_t rel[VEGA_SPLIT_MAX];                  /* tile's offset inside its split */
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const uint64_t lower = ((uint64_t)1 << lane) - 1;
+    for (int i = t; i < (BLOCK / 64) * VEGA_SPLIT_MAX; i += BLOCK) whist[i] = 0;
+    for (uint32_t i = t; i <= nw; i += BLOCK) bounds[i] = bounds_g[i];
+    rel[t] = (uint32_t)t < nw ? bh_scanned[(uint64_t)t * nblocks + blockIdx.x] - starts[t] : 0;
+    __syncthreads();
+    const uint64_t cbase = (uint64_t)blockIdx.x * TILE + (uint64_t)w * (64 * IPT);
+    uint32_t rank[IPT];
+    uint16_t dd[IPT];
+#pragma unroll
+    for (int r = 0; r < IPT; ++r) {
+        uint64_t idx = cbase + (uint64_t)r * 64 + lane;
+        bool valid = idx < n;
+        uint32_t d = valid ? split_cell(hseed, start + idx, bounds, nw) : 0;
+        uint64_t m = wave_match8(d, valid);
+        int leader = (int)__ffsll((unsigned long long)m) - 1;
+        if (leader < 0) leader = 0;
+        uint32_t b = 0;
+        if (valid && lane == leader)
+            b = atomicAdd(&whist[w * VEGA_SPLIT_MAX + d], (uint32_t)__popcll(m));
+        b = __shfl(b, leader);
+        dd[r] = (uint16_t)d;
+        rank[r] = b + (uint32_t)__popcll(m & lower);
+    }
+    __syncthreads();
+    { /* cross-wave cell offsets: whist[w][d] <- sum over waves < w (in place) */
+        uint32_t c0 = whist[t], c1 = whist[VEGA_SPLIT_MAX + t], c2 = whist[2 * VEGA_SPLIT_MAX + t];
+        __syncthreads();
+        whist[t] = 0;
+        whist[VEGA_SPLIT_MAX + t] = c0;
+        whist[2 * VEGA_SPLIT_MAX + t] = c0 + c1;
+        whist[3 * VEGA_SPLIT_MAX + t] = c0 + c1 + c2;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < IPT; ++r) {
+        uint64_t idx = cbase + (uint64_t)r * 64 + lane;
+        if (idx < n) {
+            uint32_t d = dd[r];
+            uint64_t pos = (uint64_t)rel[d] + whist[w * VEGA_SPLIT_MAX + d] + rank[r];
+            out_k[d][pos] = in_k[idx];
+            out_v[d][pos] = in_v[idx];
+        }
+    }
+}
+
+static_assert(BLOCK / 64 == 4, "k_split_scatter folds exactly four per-wave counters");
+
+size_t split_ws_bytes(uint64_t n, uint32_t nw) {
+    size_t nb = nblocks_for(n ? n : 1);
+    size_t m = (size_t)nw * nb;
+    size_t b = (m * 4 + 255) & ~(size_t)255;                    /* count matrix */
+    b += ((m / 2048 + 4096) * 4 + 255) & ~(size_t)255;          /* scan recursion partials */
+    b += (VEGA_SPLIT_MAX + 1) * 8 + (VEGA_SPLIT_MAX + 1) * 4 + 2 * VEGA_SPLIT_MAX * 8 + 5 * 256;
+    return b + 4096;
+}
+
+hipError_t split_count(hipStream_t s, uint64_t n, uint64_t start, uint64_t hseed,
+                       const uint64_t *h_bounds, uint32_t nw, SplitPlan *pl,
+                       uint64_t *h_counts, Ws &ws) {
+    if (nw == 0 || nw > VEGA_SPLIT_MAX) return hipErrorInvalidValue;
+    if (n >= (1ULL << 32)) return hipErrorNotSupported; /* u32 count matrix / scan */
+    for (uint32_t p = 0; p < nw; ++p) h_counts[p] = 0;
+    pl->bh = nullptr;
+    if (n == 0) return hipSuccess;
+    uint32_t nb = nblocks_for(n);
+    pl->bh = (uint32_t *)ws.take((size_t)nw * nb * 4);
+    pl->starts = (uint32_t *)ws.take((size_t)(nw + 1) * 4);
+    pl->bounds = (uint64_t *)ws.take((size_t)(nw + 1) * 8);
+    pl->ptr_k = (uint64_t **)ws.take((size_t)nw * 8);
+    pl->ptr_v = (uint64_t **)ws.take((size_t)nw * 8);
+    if (!pl->bh || !pl->starts || !pl->bounds || !pl->ptr_k || !pl->ptr_v)
+        return hipErrorOutOfMemory;
+    HIP_TRY(hipMemcpyAsync(pl->bounds, h_bounds, (size_t)(nw + 1) * 8, hipMemcpyHostToDevice, s));
+    {
+        ProfScope ps("split_count", s);
+        hipLaunchKernelGGL(k_split_count, dim3(nb), dim3(BLOCK), 0, s, n, start, hseed,
+                           pl->bounds, nw, nb, pl->bh);
+        HIP_TRY(hipGetLastError());
+    }
+    {
+        ProfScope ps("scan", s);
+        Ws w2 = ws;
+        HIP_TRY(scan_u32_excl(s, pl->bh, (uint64_t)nw * nb, w2));
+    }
+    hipLaunchKernelGGL(k_gather_starts, dim3((nw + 255) / 256), dim3(256), 0, s, pl->bh, nb, nw,
+                       pl->starts);
+    HIP_TRY(hipGetLastError());
+    std::vector<uint32_t> hs(nw);
+    HIP_TRY(hipMemcpyAsync(hs.data(), pl->starts, (size_t)nw * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (uint32_t p = 0; p < nw; ++p) {
+        uint64_t next = (p + 1 < nw) ? hs[p + 1] : n;
+        h_counts[p] = next - hs[p];
+    }
+    return hipSuccess;
+}
+
+hipError_t split_scatter(hipStream_t s, const uint64_t *in_k, const uint64_t *in_v, uint64_t n,
+                         uint64_t start, uint64_t hseed, uint32_t nw, const SplitPlan &pl,
+                         uint64_t *const *h_out_k, uint64_t *const *h_out_v) {
+    if (n == 0) return hipSuccess;
+    if (!pl.bh) return hipErrorInvalidValue;
+    uint32_t nb = nblocks_for(n);
+    HIP_TRY(hipMemcpyAsync(pl.ptr_k, h_out_k, (size_t)nw * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(pl.ptr_v, h_out_v, (size_t)nw * 8, hipMemcpyHostToDevice, s));
+    {
+        ProfScope ps("split_scatter", s);
+        hipLaunchKernelGGL(k_split_scatter, dim3(nb), dim3(BLOCK), 0, s, in_k, in_v, n, start,
+                           hseed, pl.bounds, nw, nb, pl.bh, pl.starts, pl.ptr_k, pl.ptr_v);
+        HIP_TRY(hipGetLastError());
+    }
+    /* the pointer tables above are read from caller memory: done before return */
+    return hipStreamSynchronize(s);
+}
+
+/* ---- take_sample's candidate ranking ---- */
+
+/* priority of candidate j and its position, the (key, value) of the sort */
+__global__ void k_sample_prio(uint64_t m, uint64_t hseed, uint64_t *prio, uint64_t *pos) {
+    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < m; j += stride) {
+        prio[j] = vega_rand_u64(hseed, j);
+        pos[j] = j;
+    }
+}
+
+__global__ void k_sample_gather(const uint64_t *cand_k, const uint64_t *cand_v,
+                                const uint64_t *order, uint64_t num, uint64_t *out_k,
+                                uint64_t *out_v) {
+    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < num; i += stride) {
+        uint64_t p = order[i];
+        out_k[i] = cand_k[p];
+        out_v[i] = cand_v[p];
+    }
+}
+
+size_t sample_rank_ws_bytes(uint64_t m) {
+    return ws_bytes_for(m) + 2 * ((m * 8 + 255) & ~(size_t)255) + 4096;
+}
+
+hipError_t sample_rank_gather(hipStream_t s, const uint64_t *cand_k, const uint64_t *cand_v,
+                              uint64_t m, uint64_t num, uint64_t hseed, uint64_t *out_k,
+                              uint64_t *out_v, Ws &ws) {
+    if (num > m) return hipErrorInvalidValue;
+    if (m >= (1ULL << 32)) return hipErrorNotSupported;
+    if (num == 0) return hipSuccess;
+    uint64_t *prio = (uint64_t *)ws.take(m * 8);
+    uint64_t *pos = (uint64_t *)ws.take(m * 8);
+    if (!prio || !pos) return hipErrorOutOfMemory;
+    uint32_t nb = nblocks_for(m);
+    uint32_t gb = nb < 2048 ? nb : 2048;
+    {
+        ProfScope ps("sample_prio", s);
+        hipLaunchKernelGGL(k_sample_prio, dim3(gb), dim3(BLOCK), 0, s, m, hseed, prio, pos);
+        HIP_TRY(hipGetLastError());
+    }
+    const uint64_t *sk, *sv;
+    HIP_TRY(radix_sort_u64(s, prio, pos, m, true, false, ws, &sk, &sv));
+    (void)sk;
+    uint32_t nbo = nblocks_for(num);
+    uint32_t go = nbo < 2048 ? nbo : 2048;
+    ProfScope ps("sample_gather", s);
+    hipLaunchKernelGGL(k_sample_gather, dim3(go), dim3(BLOCK), 0, s, cand_k, cand_v, sv, num,
+                       out_k, out_v);
+    return hipGetLastError();
+}
+
+/* ------------------------------------------------------------------ */
 /* misc host entries                                                   */
 
 hipError_t gen_uniform(hipStream_t s, int64_t *keys, int64_t *vals, uint64_t n,

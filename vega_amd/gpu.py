@@ -405,8 +405,65 @@ class Rdd:
         """min(num, n) lexicographically largest rows, descending"""
         return self._ordered(lib().vega_gpu_top, "top", num)
 
+    # --- samplers (rdd.rs:623-783); seed=None draws a 64-bit seed on the host ---
+    def sample(self, with_replacement, fraction, seed=None):
+        """Bernoulli (with_replacement false: each row kept with probability
+        fraction) or Poisson (true: each row emitted Poisson(fraction) times
+        in place) sample; row order kept, value type kept. The choice for row
+        i depends on (seed, i) only."""
+        out = ctypes.c_uint64()
+        _check(lib().vega_gpu_sample(self.ctx._c, ctypes.c_uint64(self.h),
+                                     ctypes.c_int(1 if with_replacement else 0),
+                                     ctypes.c_double(fraction),
+                                     ctypes.c_uint64(_seed(seed)), ctypes.byref(out)),
+               "sample", self.ctx._c)
+        return Rdd(self.ctx, out.value, self.vdtype)
+
+    def random_split(self, weights, seed=None):
+        """list of len(weights) disjoint Rdds whose union is this one, sized
+        in proportion to the weights; each keeps row order"""
+        w = _np(weights, np.float64)
+        outs = (ctypes.c_uint64 * max(len(w), 1))()
+        _check(lib().vega_gpu_random_split(self.ctx._c, ctypes.c_uint64(self.h),
+                                           _pp(w), ctypes.c_uint32(len(w)),
+                                           ctypes.c_uint64(_seed(seed)), outs),
+               "random_split", self.ctx._c)
+        return [Rdd(self.ctx, outs[j], self.vdtype) for j in range(len(w))]
+
+    def take_sample(self, with_replacement, num, seed=None):
+        """min(num, candidates) uniformly chosen rows in random order ->
+        (keys, vals) on the host"""
+        m = int(num)
+        if not with_replacement:  # at most n rows come back
+            m = min(m, self.count())
+        k = np.empty(m, dtype=np.int64)
+        v = np.empty(m, dtype=self.vdtype)
+        n = ctypes.c_uint64(0)
+        _check(lib().vega_gpu_take_sample(self.ctx._c, ctypes.c_uint64(self.h),
+                                          ctypes.c_int(1 if with_replacement else 0),
+                                          ctypes.c_uint64(num),
+                                          ctypes.c_uint64(_seed(seed)), _pp(k), _pp(v),
+                                          ctypes.byref(n)), "take_sample", self.ctx._c)
+        return k[:n.value], v[:n.value]
+
     def free(self):
         lib().vega_gpu_free_rdd(self.ctx._c, ctypes.c_uint64(self.h))
+
+
+def _seed(seed):
+    """the reference's Option<u64> seed: None draws 64 bits on the host"""
+    if seed is None:
+        return int.from_bytes(os.urandom(8), "little")
+    return int(seed) & 0xFFFFFFFFFFFFFFFF
+
+
+def sample_poisson_table(fraction):
+    """the integer threshold table the Poisson sampler uses (host only)"""
+    thr = np.zeros(256, dtype=np.uint64)
+    n = ctypes.c_int(0)
+    _check(lib().vega_sample_poisson_table(ctypes.c_double(fraction), _pp(thr),
+                                           ctypes.byref(n)), "sample_poisson_table")
+    return thr[:n.value].copy()
 
 
 class StatsRdd:
@@ -626,6 +683,45 @@ def dev_reduce_pairs(keys_t, vals_t, op, ws_t=None):
         ctypes.c_int(op), ctypes.byref(k), ctypes.byref(v),
         _t(ws_t), ctypes.c_size_t(ws_t.numel())), "dev_reduce_pairs")
     return k.value, v.value
+
+
+def dev_sample(keys_t, vals_t, with_replacement, fraction, seed, start=0,
+               out_k=None, out_v=None, ws_t=None):
+    """sample of device rows whose first row has the global index `start`
+    (shards sampled with their own start are the slices of the whole sample).
+    Returns (out_k, out_v, needed): the tensors trimmed to the sample. With
+    caller-given out tensors that are too small the call raises VegaGpuError
+    with rc == -5 (VEGA_ERR_CAP) and .needed = the rows the sample holds;
+    nothing is written then. Without them a count-only call sizes them."""
+    import torch
+    n = keys_t.numel()
+    if ws_t is None:
+        ws_t = alloc_ws(n, keys_t.device)
+    nout = ctypes.c_uint64(0)
+
+    def call(ok, ov, cap):
+        return lib().vega_dev_sample(
+            _stream(), _t(keys_t), _t(vals_t), ctypes.c_uint64(n),
+            ctypes.c_int(1 if with_replacement else 0), ctypes.c_double(fraction),
+            ctypes.c_uint64(_seed(seed)), ctypes.c_uint64(start),
+            _t(ok) if ok is not None else None, _t(ov) if ov is not None else None,
+            ctypes.c_uint64(cap), ctypes.byref(nout),
+            _t(ws_t), ctypes.c_size_t(ws_t.numel()))
+
+    if out_k is None:
+        seed = _seed(seed)  # one seed for the sizing call and the real one
+        rc = call(None, None, 0)
+        if rc not in (0, -5):
+            _check(rc, "dev_sample")
+        out_k = torch.empty(max(nout.value, 1), dtype=torch.int64, device=keys_t.device)
+        out_v = torch.empty(max(nout.value, 1), dtype=vals_t.dtype, device=keys_t.device)
+    rc = call(out_k, out_v, min(out_k.numel(), out_v.numel()))
+    if rc != 0:
+        err = VegaGpuError(f"dev_sample failed rc={rc} (needed {nout.value} rows)")
+        err.rc = rc
+        err.needed = nout.value
+        raise err
+    return out_k[:nout.value], out_v[:nout.value], nout.value
 
 
 def prof_enable(on=True):

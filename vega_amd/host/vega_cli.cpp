@@ -6,6 +6,9 @@
  * binary is test tooling for the C++ host layer). Exit 0 = all green.
  * `vega_cli actions` runs the reference's action tests (fold, max/min, top,
  * take_ordered, take, first, is_empty) the same way; prints `actions green`.
+ * `vega_cli sample` runs the reference's sampling tests (take_sample,
+ * random_split; tests/golden/sample.json) plus row-exact sample checks
+ * against the vega_common.h inlines; prints `sample green`.
  * Without a GPU it must FAIL LOUDLY (nonzero, message) — there is no CPU
  * fallback anywhere in the product path.
  */
@@ -124,10 +127,137 @@ static int actions_main() {
     return 0;
 }
 
+/* `vega_cli sample`: the reference's sampling tests (tests/golden/sample.json)
+ * through the vega_core.hpp mirror. Row-level expectations are recomputed
+ * here from the vega_common.h inlines — the same functions the kernels call,
+ * compiled for the host. */
+static int sample_main() {
+    using keys_t = std::vector<int64_t>;
+    setvbuf(stdout, nullptr, _IONBF, 0);
+    auto range = [](int64_t lo, int64_t hi) { /* inclusive */
+        pairs_t out;
+        for (int64_t x = lo; x <= hi; x++) out.push_back({x, 0});
+        return out;
+    };
+    auto subset = [](const keys_t &got, const pairs_t &in) {
+        for (int64_t k : got)
+            if (!std::binary_search(in.begin(), in.end(), std::make_pair(k, (int64_t)0))) return false;
+        return true;
+    };
+    try {
+        vega::Context sc;
+        /* w/o replacement, num > n (test_rdd.rs:327-334): a permutation */
+        {
+            auto in = range(1, 5);
+            auto rdd = sc.parallelize(in, 6);
+            auto got = rdd.take_sample(false, 6, 123);
+            CHECK_EQ(got.size(), (size_t)5, "take_sample(false, 6) of 5 rows == 5 rows golden");
+            CHECK_EQ(sorted(got), in, "take_sample(false, 6) is a permutation");
+        }
+        /* with replacement (test_rdd.rs:336-342) */
+        {
+            auto in = range(0, 99);
+            auto rdd = sc.parallelize(in, 5);
+            auto got = keys_of(rdd.take_sample(true, 80, 5));
+            CHECK_EQ(got.size(), (size_t)80, "take_sample(true, 80) == 80 rows golden");
+            CHECK_EQ(subset(got, in), true, "take_sample(true, 80) rows are input rows");
+            /* w/o replacement (test_rdd.rs:344-349) */
+            got = keys_of(rdd.take_sample(false, 10, 5));
+            CHECK_EQ(got.size(), (size_t)10, "take_sample(false, 10) == 10 rows golden");
+            CHECK_EQ(subset(got, in), true, "take_sample(false, 10) rows are input rows");
+            std::sort(got.begin(), got.end());
+            CHECK_EQ(std::adjacent_find(got.begin(), got.end()) == got.end(), true,
+                     "take_sample(false, 10) rows are distinct");
+            CHECK_EQ(rdd.take_sample(false, 0, 5).size(), (size_t)0, "take_sample(num = 0) empty");
+            CHECK_EQ(sc.parallelize({}, 2).take_sample(true, 4, 5).size(), (size_t)0,
+                     "take_sample on empty rdd");
+        }
+        /* random_split (test_rdd.rs:622-652): 600 rows, weights 1:2:3 */
+        {
+            auto in = range(1, 600);
+            auto rdd = sc.parallelize(in, 3);
+            const std::vector<double> w{1.0, 2.0, 3.0};
+            const uint64_t bounds[4] = {0, vega_sample_threshold(1.0 / 6.0),
+                                        vega_sample_threshold(1.0 / 6.0 + 2.0 / 6.0),
+                                        VEGA_SAMPLE_ONE};
+            for (uint64_t seed : {123ull, 0ull, 7ull}) {
+                auto parts = rdd.random_split(w, seed);
+                CHECK_EQ(parts.size(), (size_t)3, "random_split gives 3 rdds golden");
+                std::vector<keys_t> want(3);
+                for (uint64_t i = 0; i < 600; i++)
+                    want[vega_sample_split_cell(vega_sample_draw(seed, i), bounds, 3)]
+                        .push_back(in[i].first);
+                size_t total = 0;
+                bool sized = true, exact = true;
+                for (int j = 0; j < 3; j++) {
+                    auto got = keys_of(parts[j].collect());
+                    total += got.size();
+                    long off = (long)got.size() - 100 * (j + 1);
+                    sized = sized && off > -50 && off < 50;
+                    exact = exact && got == want[j];
+                    parts[j].free();
+                }
+                CHECK_EQ(total, (size_t)600, "random_split sizes sum to 600 golden");
+                CHECK_EQ(sized, true, "random_split sizes within 50 of 100/200/300 golden");
+                /* equal to the disjoint host partition: disjoint and complete */
+                CHECK_EQ(exact, true, "random_split == host cells of vega_common.h");
+                if (seed == 123)
+                    CHECK_EQ((keys_t{(int64_t)want[0].size(), (int64_t)want[1].size(),
+                                     (int64_t)want[2].size()}),
+                             (keys_t{90, 206, 304}), "seed 123 splits 90/206/304");
+            }
+            /* split 0 is the Bernoulli sample of its share */
+            auto parts = rdd.random_split(w, 123);
+            CHECK_EQ(parts[0].collect(), rdd.sample(false, 1.0 / 6.0, 123).collect(),
+                     "split 0 == sample(false, w0/sum)");
+        }
+        /* sample: Bernoulli and Poisson against the host inlines */
+        {
+            pairs_t in;
+            for (int64_t x = 0; x < 10000; x++) in.push_back({x * 3, -x});
+            auto rdd = sc.parallelize(in, 4);
+            pairs_t want;
+            const uint64_t t = vega_sample_threshold(0.25);
+            for (uint64_t i = 0; i < in.size(); i++)
+                if (vega_sample_draw(77, i) < t) want.push_back(in[i]);
+            CHECK_EQ(rdd.sample(false, 0.25, 77).collect(), want, "sample(false, 0.25) row-exact");
+            uint64_t thr[VEGA_SAMPLE_TABLE_MAX];
+            int len = 0;
+            CHECK_EQ(vega_sample_poisson_table(2.0, thr, &len), VEGA_OK, "poisson table(2.0)");
+            want.clear();
+            for (uint64_t i = 0; i < in.size(); i++) {
+                uint32_t c = vega_sample_poisson_count(vega_sample_draw(78, i), thr, (uint32_t)len);
+                for (uint32_t j = 0; j < c; j++) want.push_back(in[i]);
+            }
+            CHECK_EQ(rdd.sample(true, 2.0, 78).collect(), want, "sample(true, 2.0) row-exact");
+            CHECK_EQ(want.size() > in.size(), true, "sample(true, 2.0) expands");
+            CHECK_EQ(rdd.sample(false, 0.5).count() > 0, true, "sample with a drawn seed");
+            bool threw = false;
+            try {
+                (void)rdd.sample(false, 1.5, 1);
+            } catch (const vega::VegaError &e) {
+                threw = strstr(e.what(), "rc=-1") != nullptr;
+            }
+            CHECK_EQ(threw, true, "sample(false, 1.5) is INVALID");
+            CHECK_EQ(rdd.collect(), in, "source rdd unchanged");
+        }
+    } catch (const std::exception &e) {
+        fprintf(stderr, "vega_cli: FATAL: %s\n", e.what());
+        return 1;
+    }
+    if (fails) {
+        fprintf(stderr, "vega_cli: %d check(s) FAILED\n", fails);
+        return 1;
+    }
+    printf("vega_cli: sample green\n");
+    return 0;
+}
+
 int main(int argc, char **argv) {
     if (argc >= 2 && strcmp(argv[1], "actions") == 0) return actions_main();
+    if (argc >= 2 && strcmp(argv[1], "sample") == 0) return sample_main();
     if (argc < 2 || strcmp(argv[1], "selftest") != 0) {
-        fprintf(stderr, "usage: vega_cli selftest|actions\n");
+        fprintf(stderr, "usage: vega_cli selftest|actions|sample\n");
         return 2;
     }
     setvbuf(stdout, nullptr, _IONBF, 0); /* keep progress visible on a crash */

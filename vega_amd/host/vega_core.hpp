@@ -6,7 +6,8 @@
  * semantics: Context (context.rs:147-164), make_rdd/parallelize
  * (context.rs:406-442), PairRdd ops (pair_rdd.rs:20-171), actions
  * collect/count (rdd.rs:420-447) and reduce/fold/aggregate/min/max/take/
- * first/is_empty/top/take_ordered. Same names, same argument meaning, same
+ * first/is_empty/top/take_ordered, and the samplers sample/random_split/
+ * take_sample (rdd.rs:623-783). Same names, same argument meaning, same
  * error behavior (throws on failure — the reference Results/panics).
  *
  * Header-only; link against libvega_gpu.so.
@@ -16,6 +17,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <optional>
+#include <random>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -235,6 +237,38 @@ class PairRdd {
         return zip(k, v, n);
     }
 
+    /* ---- samplers; seed = nullopt draws one on the host (Option<u64>) ---- */
+    /* rdd.rs:690-702: Bernoulli (each row with probability fraction) or,
+     * with replacement, Poisson(fraction) copies of each row in place */
+    PairRdd sample(bool with_replacement, double fraction,
+                   std::optional<uint64_t> seed = std::nullopt) const {
+        vega_rdd_t out = 0;
+        check(vega_gpu_sample(c_, h_, with_replacement ? 1 : 0, fraction, seed_of(seed), &out),
+              "sample", c_);
+        return PairRdd(c_, out, f64_);
+    }
+    /* rdd.rs:623-672: disjoint rdds sized by the weights, union = this rdd */
+    std::vector<PairRdd> random_split(const std::vector<double> &weights,
+                                      std::optional<uint64_t> seed = std::nullopt) const {
+        std::vector<vega_rdd_t> hs(weights.size() ? weights.size() : 1, 0);
+        check(vega_gpu_random_split(c_, h_, weights.data(), (uint32_t)weights.size(),
+                                    seed_of(seed), hs.data()),
+              "random_split", c_);
+        std::vector<PairRdd> out;
+        for (size_t j = 0; j < weights.size(); j++) out.push_back(PairRdd(c_, hs[j], f64_));
+        return out;
+    }
+    /* rdd.rs:717-783: num rows chosen uniformly, in random order */
+    std::vector<row_t> take_sample(bool with_replacement, uint64_t num,
+                                   std::optional<uint64_t> seed = std::nullopt) const {
+        uint64_t m = with_replacement ? num : std::min<uint64_t>(num, count()), n = 0;
+        std::vector<int64_t> k(m), v(m);
+        check(vega_gpu_take_sample(c_, h_, with_replacement ? 1 : 0, num, seed_of(seed), k.data(),
+                                   v.data(), &n),
+              "take_sample", c_);
+        return zip(k, v, n);
+    }
+
     void free() {
         if (c_ && h_) vega_gpu_free_rdd(c_, h_);
         h_ = 0;
@@ -248,6 +282,11 @@ class PairRdd {
         std::vector<std::pair<int64_t, int64_t>> out(n);
         for (uint64_t i = 0; i < n; i++) out[i] = {k[i], v[i]};
         return out;
+    }
+    static uint64_t seed_of(const std::optional<uint64_t> &seed) {
+        if (seed) return *seed;
+        std::random_device rd;
+        return ((uint64_t)rd() << 32) ^ (uint64_t)rd();
     }
     vega_ctx_t *c_ = nullptr;
     vega_rdd_t h_ = 0;
