@@ -346,6 +346,26 @@ int vega_dev_sort_stats_i64(void *stream, const int64_t *in_k, const int64_t *in
                             int64_t *out_min, int64_t *out_max, uint64_t *h_nout,
                             void *d_ws, size_t ws_bytes);
 
+/* diagnostic: the grouped rows (equal keys adjacent) that vega_dev_sort_reduce
+ * and vega_dev_sort_stats_i64 aggregate, as SoA columns of n rows. in_k/in_v
+ * are NOT modified. route picks how the hash order is finished: 0 automatic,
+ * 1 four hash passes + cleanup, 2 three hash passes + bucket-local finish
+ * (1 and 2 also pin the hash strategy; 2 still falls back to 1 when a bucket
+ * or collision run exceeds the finish kernel's caps). Both routes leave the
+ * same rows. *route_taken (host, optional): the route that produced the
+ * result, 0 if no hash route ran (narrow keys, n <= 1). Synchronizes the
+ * stream internally. */
+int vega_dev_group_rows_i64(void *stream, const int64_t *in_k, const int64_t *in_v, uint64_t n,
+                            int route, int64_t *out_k, int64_t *out_v,
+                            void *d_ws, size_t ws_bytes, int *route_taken);
+
+/* diagnostic, host arithmetic only (no device call): the rows per occupied
+ * hash bucket (bucket = bits 8..31 of the low 32 hash bits) that the automatic
+ * route estimates for n rows from ns <= 2048 sampled keys (HOST array). Route
+ * 0 takes the bucket finish only when no sampled key repeats and this
+ * estimate is at least 24. */
+int vega_diag_bucket_rows(const int64_t *sample_keys, uint32_t ns, uint64_t n, double *out);
+
 /* stable LSB radix sort by signed-i64 key (sort_by_key). In-place semantics:
  * result lands back in keys/vals. */
 int vega_dev_sort_pairs_i64(void *stream, int64_t *keys, int64_t *vals,

@@ -1584,6 +1584,30 @@ int vega_dev_sort_reduce(void *stream, const int64_t *in_k, const void *in_v,
     return e == hipSuccess ? VEGA_OK : (e == hipErrorOutOfMemory ? VEGA_ERR_NOMEM : VEGA_ERR_HIP);
 }
 
+/* diagnostic, host only: see vega_gpu.h */
+int vega_diag_bucket_rows(const int64_t *sample_keys, uint32_t ns, uint64_t n, double *out) {
+    if (!sample_keys || !out || ns == 0 || ns > 2048) return VEGA_ERR_INVALID;
+    *out = bucket_rows_estimate((const uint64_t *)sample_keys, ns, n);
+    return VEGA_OK;
+}
+
+/* diagnostic: the grouped rows vega_dev_sort_reduce aggregates; see vega_gpu.h */
+int vega_dev_group_rows_i64(void *stream, const int64_t *in_k, const int64_t *in_v, uint64_t n,
+                            int route, int64_t *out_k, int64_t *out_v,
+                            void *d_ws, size_t ws_bytes, int *route_taken) {
+    if (route_taken) *route_taken = 0;
+    if (route < 0 || route > 2) return VEGA_ERR_INVALID;
+    if (n >= (1ULL << 32)) return VEGA_ERR_UNSUPPORTED;
+    if (!n) return VEGA_OK;
+    if (!in_k || !in_v || !out_k || !out_v) return VEGA_ERR_INVALID;
+    if (!d_ws || ws_bytes < ws_bytes_for(n)) return VEGA_ERR_CAP;
+    Ws ws(d_ws, ws_bytes);
+    hipError_t e = group_rows((hipStream_t)stream, (const uint64_t *)in_k, (const uint64_t *)in_v,
+                              n, route, (uint64_t *)out_k, (uint64_t *)out_v, ws, route_taken);
+    if (e == hipErrorNotSupported) return VEGA_ERR_UNSUPPORTED;
+    return e == hipSuccess ? VEGA_OK : (e == hipErrorOutOfMemory ? VEGA_ERR_NOMEM : VEGA_ERR_HIP);
+}
+
 /* reduce-side grouping + fused (count, sum, min, max) aggregate; see
  * vega_gpu.h. The five outputs take 16-B pair stores on the all-distinct
  * fast path, hence the alignment requirement. */

@@ -65,7 +65,18 @@ hipError_t radix_sort_u64(hipStream_t s, const uint64_t *in_k, const uint64_t *i
 hipError_t group_sort_u64(hipStream_t s, const uint64_t *in_k, const uint64_t *in_v,
                           uint64_t n, int force_hbytes, int *order_tag,
                           int want_packed, int *out_packed, Ws &ws,
-                          const uint64_t **res_k, const uint64_t **res_v);
+                          const uint64_t **res_k, const uint64_t **res_v,
+                          int route = 0, int *route_taken = nullptr);
+
+/* rows per occupied hash bucket that group_sort_u64's automatic route
+ * estimates from its key sample (host arithmetic only; ns <= 2048) */
+double bucket_rows_estimate(const uint64_t *samp, uint32_t ns, uint64_t n);
+
+/* diagnostic: the grouped rows group_sort_reduce aggregates, as SoA columns.
+ * route 0 automatic, 1 four hash passes + cleanup, 2 three passes + bucket
+ * finish (falls back to 1 on its flag); *route_taken as in group_sort_u64. */
+hipError_t group_rows(hipStream_t s, const uint64_t *in_k, const uint64_t *in_v, uint64_t n,
+                      int route, uint64_t *out_k, uint64_t *out_v, Ws &ws, int *route_taken);
 
 /* segmented aggregate over key-sorted rows: one output row per equal-key
  * run. op: VEGA_OP_*. Returns #segments in *h_nout (after stream sync). */

@@ -21,6 +21,7 @@
  */
 
 #include <hip/hip_runtime.h>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -963,10 +964,46 @@ static hipError_t scatter_pass(hipStream_t s, const uint64_t *in_k, const uint64
 /* ------------------------------------------------------------------ */
 /* radix sort driver                                                   */
 
+/* estimated rows per occupied bucket of the hash order (bucket = bits 8..31
+ * of h32) for n rows, from ns <= 2048 sampled keys: n / B. B comes from the
+ * number d of distinct bucket ids among the sampled keys: ns draws from B
+ * equally likely buckets hit B (1 - exp(-ns / B)) of them. With fewer than 8
+ * coinciding draws the sample cannot tell B from "all 2^24", which is what a
+ * spread-out key set gives, so that is assumed (PERF-ONLY). */
+double bucket_rows_estimate(const uint64_t *samp, uint32_t ns, uint64_t n) {
+    static thread_local uint32_t bslot[4096];
+    static thread_local bool bused[4096];
+    if (ns > 2048) ns = 2048;
+    memset(bused, 0, sizeof bused);
+    uint32_t d = 0;
+    for (uint32_t i = 0; i < ns; ++i) {
+        uint32_t b = ((uint32_t)vega_hash_u64(samp[i]) >> 8) & 0xFFFFFFu;
+        uint32_t at = (uint32_t)vega_hash_u64(b) & 4095u;
+        while (bused[at] && bslot[at] != b) at = (at + 1) & 4095u;
+        d += !bused[at];
+        bused[at] = true;
+        bslot[at] = b;
+    }
+    double B = 16777216.0;
+    if (ns - d >= 8) { /* bisect B (1 - exp(-ns / B)) = d on [d, 2^24] */
+        double lo = d, hi = B;
+        for (int it = 0; it < 48; ++it) {
+            double mid = 0.5 * (lo + hi);
+            if (mid * (1.0 - exp(-(double)ns / mid)) < d) lo = mid; else hi = mid;
+        }
+        B = hi;
+    }
+    return (double)n / B;
+}
+
 /* estimate # of non-degenerate radix passes from a 2048-key strided sample
- * (PERF-ONLY: callers re-verify with the exact hist8 before skipping) */
+ * (PERF-ONLY: callers re-verify with the exact hist8 before skipping).
+ * *repeat (optional): the sample holds some key value twice — a heavy hitter
+ * is likely, so buckets of the hash order may be long (PERF-ONLY as well).
+ * *bucket_rows (optional): bucket_rows_estimate of the sample. */
 static hipError_t sample_active_passes(hipStream_t s, const uint64_t *in_k, uint64_t n,
-                                       Ws &ws, int *a_est) {
+                                       Ws &ws, int *a_est, bool *repeat = nullptr,
+                                       double *bucket_rows = nullptr) {
     uint32_t ns = (uint32_t)((n < 2048) ? n : 2048);
     uint64_t *samp_d = (uint64_t *)ws.take(2048 * 8);
     if (!samp_d) return hipErrorOutOfMemory;
@@ -986,6 +1023,20 @@ static hipError_t sample_active_passes(hipStream_t s, const uint64_t *in_k, uint
         active += nz > 1;
     }
     *a_est = active;
+    if (repeat) { /* open-addressing set, 2 slots per key: a few microseconds */
+        static thread_local uint64_t slot[4096];
+        static thread_local bool used[4096];
+        memset(used, 0, sizeof used);
+        *repeat = false;
+        for (uint32_t i = 0; i < ns && !*repeat; ++i) {
+            uint32_t at = (uint32_t)vega_hash_u64(samp[i]) & 4095u;
+            while (used[at] && slot[at] != samp[i]) at = (at + 1) & 4095u;
+            *repeat = used[at];
+            used[at] = true;
+            slot[at] = samp[i];
+        }
+    }
+    if (bucket_rows) *bucket_rows = bucket_rows_estimate(samp, ns, n);
     return hipSuccess;
 }
 
@@ -1231,6 +1282,260 @@ __global__ void k_group_cleanup_long(const uint64_t *k, const uint32_t *h32,
     }
 }
 
+/* Bucket-local finish of the relaxed hash route. After three stable passes
+ * over hash bytes 1..3 the rows lie in ascending BUCKET order (bucket = bits
+ * 8..31 of h32; ~n/2^24 rows each), so the fourth pass and the cleanup only
+ * permute rows inside a bucket. Per FIN_FT-row tile a workgroup stages the
+ * tile plus FIN_SLACK rows either side in LDS, re-hashes the keys, orders
+ * every bucket that intersects the tile by (h32, input position) — the
+ * stable sort by hash byte 0, as one wave-private counting sort per bucket —
+ * applies k_group_cleanup's relaxed rule to each equal-h32 run, and stores
+ * the rows whose final position lies in its own tile. Buckets across a tile
+ * edge are computed for both tiles, identically; each row is stored once.
+ * Blocks share only *err: it is set when a bucket does not close inside the
+ * slack, holds more than FIN_BUCKET_CAP rows, or a dirty run exceeds 64
+ * rows, and the caller then runs the four-pass route from the untouched
+ * input.
+ * Blocks are persistent (FIN_GRID of them; block b takes tiles b, b +
+ * FIN_GRID, ...): the next tile's rows are loaded into registers while the
+ * current tile is ordered in LDS. */
+constexpr int FIN_FT = 2048, FIN_SLACK = 256, FIN_BUCKET_CAP = 256, FIN_B = 512;
+constexpr int FIN_SPAN = FIN_FT + 2 * FIN_SLACK;
+constexpr int FIN_LPT = FIN_SPAN / FIN_B; /* staged rows per thread */
+constexpr int FIN_GRID = 512;             /* 2 blocks per CU */
+/* the automatic route takes the finish only from this many (estimated) rows
+ * per bucket: the kernel's time grows with the buckets per tile. Measured on
+ * uniform keys, finish route against four passes + cleanup: +0.5 ms at 15
+ * rows per bucket (2.5e8 rows), -0.1 ms at 21 (3.5e8), -0.5 ms at 24 (4.1e8),
+ * -1.3 ms at 33 (5.5e8), -3.4 ms at 60 (1e9); three calls each, spread
+ * <= 0.15 ms (profiles/bucket_finish_route_sweep.json) */
+constexpr double FIN_MIN_BUCKET_ROWS = 24.0;
+static_assert(FIN_SPAN % FIN_B == 0 && FIN_FT % FIN_B == 0, "whole rounds per block");
+static_assert(FIN_SPAN <= 65536, "span positions are kept as u16");
+static_assert(FIN_SLACK >= FIN_BUCKET_CAP, "a capped bucket must close inside the slack");
+static_assert(FIN_BUCKET_CAP % 64 == 0, "a bucket is ranked in whole wave rounds");
+
+/* orders one wave's LDS accesses across lanes: the hardware runs a wave's
+ * LDS instructions in program order, this keeps the compiler to it */
+__device__ __forceinline__ void fin_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+/* inclusive wave64 prefix sum in registers (DPP: shifts inside each row of
+ * 16 lanes, then lane 15 of rows 0/2 into rows 1/3 and lane 31 into the
+ * upper half) — no LDS round trips, unlike a __shfl_up ladder */
+__device__ __forceinline__ uint32_t fin_wave_scan_incl(uint32_t x) {
+    int v = (int)x;
+    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false); /* row_shr:1 */
+    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false); /* row_shr:2 */
+    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, false); /* row_shr:4 */
+    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false); /* row_shr:8 */
+    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false); /* row_bcast:15 */
+    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false); /* row_bcast:31 */
+    return (uint32_t)v;
+}
+
+/* one equal-h32 run of len >= 2 at final positions [p, p + len): first back
+ * to input order (ascending staged index — the counting sort places equal
+ * digits in arbitrary order), then k_group_cleanup's relaxed rule */
+__device__ __forceinline__ void fin_fix_run(const ulonglong2 *s_row, uint16_t *s_src,
+                                            int p, int len, int *err) {
+    const int pe = p + len;
+    for (int x = p + 1; x < pe; x++) {
+        uint16_t sx = s_src[x];
+        int y = x;
+        while (y > p && s_src[y - 1] > sx) {
+            s_src[y] = s_src[y - 1];
+            y--;
+        }
+        s_src[y] = sx;
+    }
+    if (len == 2) return; /* nothing to group either way */
+    uint32_t breaks = 0;
+    uint64_t prev = s_row[s_src[p]].x;
+    for (int x = p + 1; x < pe && breaks < 2; x++) {
+        uint64_t cx = s_row[s_src[x]].x;
+        breaks += cx != prev;
+        prev = cx;
+    }
+    if (breaks <= 1) return;
+    if (len > 64) { *err = 1; return; }
+    for (int x = p + 1; x < pe; x++) {
+        uint16_t sx = s_src[x];
+        uint64_t kx = s_row[sx].x;
+        int y = x;
+        while (y > p && s_row[s_src[y - 1]].x > kx) {
+            s_src[y] = s_src[y - 1];
+            y--;
+        }
+        s_src[y] = sx;
+    }
+}
+
+__global__ __launch_bounds__(FIN_B) void k_bucket_finish(const uint64_t *in, uint64_t *out,
+                                                         uint64_t n, int *err) {
+    __shared__ ulonglong2 s_row[FIN_SPAN]; /* staged rows, input order */
+    __shared__ uint32_t s_h[FIN_SPAN];     /* h32 per staged row */
+    __shared__ uint16_t s_src[FIN_SPAN];   /* final position -> staged row */
+    __shared__ uint16_t s_bk[FIN_SPAN];    /* first row of each bucket in the span */
+    __shared__ __attribute__((aligned(16))) uint32_t s_cnt[FIN_B / 64][256]; /* per wave */
+    __shared__ int s_lo, s_hi, s_bad, s_nbk;
+
+    const uint32_t ntiles = (uint32_t)((n + FIN_FT - 1) / FIN_FT);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+
+    /* staged rows [g0, g0 + m) of a tile */
+    auto bounds = [&](uint32_t tile, uint64_t *g0, int *m) {
+        const uint64_t t0 = (uint64_t)tile * FIN_FT;
+        const uint64_t t1 = (n - t0 < FIN_FT) ? n : t0 + FIN_FT;
+        *g0 = (t0 < FIN_SLACK) ? 0 : t0 - FIN_SLACK;
+        *m = (int)(((n - t1 < FIN_SLACK) ? n : t1 + FIN_SLACK) - *g0);
+    };
+    ulonglong2 r[FIN_LPT];
+    auto fetch = [&](uint32_t tile) {
+        uint64_t g0;
+        int m;
+        bounds(tile, &g0, &m);
+        /* clamped, not guarded: a branch around each load would make every
+         * one wait for the one before it */
+#pragma unroll
+        for (int q = 0; q < FIN_LPT; ++q) {
+            int li = q * FIN_B + threadIdx.x;
+            r[q] = ((const ulonglong2 *)in)[g0 + (li < m ? li : m - 1)];
+        }
+    };
+
+    /* fills s_src for the whole buckets meeting the tile [a0, a1) (span-local).
+     * False, for the whole block, when the tile cannot be finished here. */
+    auto order_tile = [&](uint64_t g0, int m, int a0, int a1) -> bool {
+        /* rows are bucket-ascending: the last foreign row left of the tile
+         * and the first one right of it bound the span */
+        const uint32_t bfirst = s_h[a0] >> 8, blast = s_h[a1 - 1] >> 8;
+        for (int li = threadIdx.x; li < a0; li += FIN_B)
+            if ((s_h[li] >> 8) != bfirst && (s_h[li + 1] >> 8) == bfirst) s_lo = li + 1;
+        for (int li = a1 + threadIdx.x; li < m; li += FIN_B)
+            if ((s_h[li] >> 8) != blast && (s_h[li - 1] >> 8) == blast) s_hi = li;
+        __syncthreads();
+        const int lo = s_lo, hi = s_hi;
+        /* not closed: the bucket may continue in rows that are not staged */
+        if ((lo == 0 && g0 > 0) || (hi == m && g0 + m < n)) {
+            if (threadIdx.x == 0) *err = 1;
+            return false;
+        }
+        /* bucket heads, in any order */
+        for (int li = lo + threadIdx.x; li < hi; li += FIN_B)
+            if (li == lo || (s_h[li] >> 8) != (s_h[li - 1] >> 8))
+                s_bk[atomicAdd(&s_nbk, 1)] = (uint16_t)li;
+        __syncthreads();
+
+        /* one wave per bucket: counting sort by hash byte 0 on the wave's own
+         * 256 counters — count (the fetched old count is the row's slot among
+         * its equals), exclusive scan, place; then the lane that owns a digit
+         * puts that digit's run right. The wave's LDS operations execute in
+         * program order, so the steps need no block barrier. */
+        /* (the loop is a chain of dependent LDS round trips: the next bucket's
+         * start is read one iteration ahead, and the reads that depend only on
+         * the start go out together) */
+        uint32_t *cnt = s_cnt[w];
+        const int nbk = s_nbk;
+        int bs_next = (w < nbk) ? s_bk[w] : 0;
+        for (int e = w; e < nbk; e += FIN_B / 64) {
+            const int bs = bs_next;
+            bs_next = (e + FIN_B / 64 < nbk) ? s_bk[e + FIN_B / 64] : 0;
+            ((uint4 *)cnt)[lane] = make_uint4(0, 0, 0, 0);
+            const int over = bs + FIN_BUCKET_CAP < hi ? bs + FIN_BUCKET_CAP : bs;
+            const int l0 = bs + lane < hi ? bs + lane : bs;
+            const uint32_t b = s_h[bs] >> 8, bover = s_h[over] >> 8, h0 = s_h[l0];
+            fin_wave_sync();
+            if (over != bs && bover == b) {
+                if (lane == 0) s_bad = 1; /* more than FIN_BUCKET_CAP rows */
+                continue;
+            }
+            uint32_t hh[FIN_BUCKET_CAP / 64], old[FIN_BUCKET_CAP / 64];
+            bool val[FIN_BUCKET_CAP / 64];
+            bool go = true;
+#pragma unroll
+            for (int q = 0; q < FIN_BUCKET_CAP / 64; ++q) {
+                val[q] = false;
+                if (go) {
+                    const int li = bs + 64 * q + lane;
+                    hh[q] = q == 0 ? h0 : (li < hi ? s_h[li] : 0);
+                    val[q] = li < hi && (hh[q] >> 8) == b;
+                    if (val[q]) old[q] = atomicAdd(&cnt[hh[q] & 0xFF], 1u);
+                    go = __all(val[q]);
+                }
+            }
+            fin_wave_sync();
+            const uint4 c = ((const uint4 *)cnt)[lane];
+            const uint32_t sum = c.x + c.y + c.z + c.w;
+            const uint32_t ex = fin_wave_scan_incl(sum) - sum;
+            ((uint4 *)cnt)[lane] = make_uint4(ex, ex + c.x, ex + c.x + c.y, ex + c.x + c.y + c.z);
+            fin_wave_sync();
+#pragma unroll
+            for (int q = 0; q < FIN_BUCKET_CAP / 64; ++q)
+                if (val[q])
+                    s_src[bs + (int)(cnt[hh[q] & 0xFF] + old[q])] = (uint16_t)(bs + 64 * q + lane);
+            fin_wave_sync();
+            /* equal byte 0 inside a bucket == equal h32: digit d's rows are a run */
+            if (c.x >= 2) fin_fix_run(s_row, s_src, bs + (int)ex, (int)c.x, err);
+            if (c.y >= 2) fin_fix_run(s_row, s_src, bs + (int)(ex + c.x), (int)c.y, err);
+            if (c.z >= 2) fin_fix_run(s_row, s_src, bs + (int)(ex + c.x + c.y), (int)c.z, err);
+            if (c.w >= 2)
+                fin_fix_run(s_row, s_src, bs + (int)(ex + c.x + c.y + c.z), (int)c.w, err);
+            fin_wave_sync();
+        }
+        __syncthreads();
+        if (s_bad) { /* oversized bucket: s_src is incomplete */
+            if (threadIdx.x == 0) *err = 1;
+            return false;
+        }
+        return true;
+    };
+
+    uint32_t tile = blockIdx.x;
+    if (tile < ntiles) fetch(tile);
+    while (tile < ntiles) {
+        const uint64_t t0 = (uint64_t)tile * FIN_FT;
+        const uint64_t t1 = (n - t0 < FIN_FT) ? n : t0 + FIN_FT;
+        uint64_t g0;
+        int m;
+        bounds(tile, &g0, &m);
+        const int a0 = (int)(t0 - g0), a1 = (int)(t1 - g0); /* tile, span-local */
+        if (threadIdx.x == 0) { s_lo = 0; s_hi = m; s_bad = 0; s_nbk = 0; }
+#pragma unroll
+        for (int q = 0; q < FIN_LPT; ++q) {
+            int li = q * FIN_B + threadIdx.x;
+            if (li < m) {
+                s_row[li] = r[q];
+                s_h[li] = (uint32_t)vega_hash_u64(r[q].x);
+            }
+        }
+        __syncthreads();
+        const uint32_t next = tile + gridDim.x;
+        if (next < ntiles) fetch(next);
+        if (order_tile(g0, m, a0, a1)) {
+#pragma unroll
+            for (int q = 0; q < FIN_FT / FIN_B; ++q) {
+                int p = a0 + q * FIN_B + threadIdx.x;
+                if (p < a1) ((ulonglong2 *)out)[g0 + p] = s_row[s_src[p]];
+            }
+        }
+        __syncthreads(); /* LDS is restaged next */
+        tile = next;
+    }
+}
+
+/* packed (k,v) rows -> SoA columns (diagnostic entry only) */
+__global__ void k_unpack_rows(const uint64_t *pk, uint64_t n, uint64_t *k, uint64_t *v) {
+    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        ulonglong2 r = ((const ulonglong2 *)pk)[i];
+        k[i] = r.x;
+        v[i] = r.y;
+    }
+}
+
 /* group equal keys adjacently (reduce path — no total order contract).
  * Adaptive: if the per-byte key histograms show <= 5 active radix passes,
  * the plain key sort is cheaper; else 5 hash-byte passes + cleanup (with a
@@ -1240,14 +1545,25 @@ __global__ void k_group_cleanup_long(const uint64_t *k, const uint32_t *h32,
  * unsigned-lexicographic (4 hash-byte passes + h32 cleanup). force_hbytes=4
  * pins the hash order regardless of n (joins need a stable comparator);
  * 0 = adaptive (reduce path). */
+/* route (hash strategy, relaxed contract, 4 hash bytes, packed result):
+ *   0 automatic: three passes + k_bucket_finish when the key sample shows no
+ *     repeated key and at least FIN_MIN_BUCKET_ROWS rows per bucket, else
+ *     four passes + cleanup;
+ *   1 / 2 pin four passes + cleanup / three passes + finish, and pin the hash
+ *     strategy with them (diagnostic entry only).
+ * *route_taken (optional): 1 or 2 for the route that produced the result —
+ * 1 also when the finish raised its flag and the four passes ran after it —
+ * 0 when no hash route did (n <= 1, narrow keys). */
 hipError_t group_sort_u64(hipStream_t s, const uint64_t *in_k, const uint64_t *in_v,
                           uint64_t n, int force_hbytes, int *order_tag,
                           int want_packed, int *out_packed, Ws &ws,
-                          const uint64_t **res_k, const uint64_t **res_v) {
+                          const uint64_t **res_k, const uint64_t **res_v,
+                          int route, int *route_taken) {
     *res_k = in_k;
     *res_v = in_v;
     if (out_packed) *out_packed = 0;
     if (order_tag) *order_tag = 0;
+    if (route_taken) *route_taken = 0;
     if (n <= 1) return hipSuccess;
     if (n >= (1ULL << 32)) return hipErrorNotSupported; /* u32 hist/scan limit (vega_gpu.h) */
     uint32_t nb = nblocks_for(n);
@@ -1339,10 +1655,12 @@ hipError_t group_sort_u64(hipStream_t s, const uint64_t *in_k, const uint64_t *i
 
     /* sampled strategy choice (perf-only; both strategies are exact) */
     int a_est = 8;
-    HIP_TRY(sample_active_passes(s, in_k, n, ws, &a_est));
+    bool samp_repeat = false;
+    double bucket_rows = 0;
+    HIP_TRY(sample_active_passes(s, in_k, n, ws, &a_est, &samp_repeat, &bucket_rows));
 
     const uint64_t *cur_k = in_k, *cur_v = in_v;
-    if (a_est <= 5) {
+    if (a_est <= 5 && route == 0) {
         int active = 8;
         HIP_TRY(exact_hists(false, 8, &active));
         if (active <= 5) { /* narrow keys: skipped key sort groups exactly */
@@ -1364,6 +1682,45 @@ hipError_t group_sort_u64(hipStream_t s, const uint64_t *in_k, const uint64_t *i
     HIP_TRY(exact_hists(true, hbytes, &active5));
     const bool keep_pk = want_packed != 0; /* final pass stays packed:
         the SoA+h32 unpack pass measured 12.1 ms vs 8.6 interior */
+    if (!strict && hbytes == 4 && keep_pk && route != 1 &&
+        (route == 2 || (!samp_repeat && bucket_rows >= FIN_MIN_BUCKET_ROWS))) {
+        /* finish route: bytes 1..3 leave the rows bucket-ordered in pA; the
+         * byte-0 order and the cleanup are bucket-local (k_bucket_finish) */
+        for (int i = 1; i < 4; ++i) {
+            uint64_t *dk = (i & 1) ? pA : pB;
+            HashByteDigit df{8 * i};
+            HIP_TRY(scatter_pass_osw(s, i == 1 ? in_k : cur_k, i == 1 ? in_v : nullptr,
+                                     n, gbase_d + i * 256, desc, ticket, dk, nullptr, nullptr,
+                                     d_abort, ff_d, ptag_ctr++, true, i > 1, true, df, "radix_scatter"));
+            cur_k = dk;
+        }
+        HIP_TRY(hipMemsetAsync(d_err, 0, 4, s));
+        {
+            ProfScope ps("group_cleanup", s); /* this route's cleanup stage */
+            ProfScope pk("bucket_finish", s);
+            const uint32_t ntiles = (uint32_t)((n + FIN_FT - 1) / FIN_FT);
+            hipLaunchKernelGGL(k_bucket_finish, dim3(ntiles < FIN_GRID ? ntiles : FIN_GRID),
+                               dim3(FIN_B), 0, s, cur_k, pB, n, d_err);
+            HIP_TRY(hipGetLastError());
+        }
+        int fl[2] = {0, 0};
+        HIP_TRY(hipMemcpyAsync(&fl[0], d_err, 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(&fl[1], d_abort, 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (fl[1]) return hipErrorUnknown; /* lookback bailed: fail loudly */
+        if (!fl[0]) {
+            if (out_packed) *out_packed = 1;
+            if (route_taken) *route_taken = 2;
+            *res_k = pB;
+            *res_v = nullptr;
+            return hipSuccess;
+        }
+        /* a bucket or dirty run over its cap: the four passes below start
+         * again from in_k / in_v (gbase_d still holds all four bases) */
+        cur_k = in_k;
+        cur_v = in_v;
+    }
+    if (route_taken) *route_taken = 1;
     for (int i = 0; i < hbytes; ++i) {
         bool in_pk = i > 0, out_pk = keep_pk || (i < hbytes - 1);
         bool last = i == hbytes - 1;
@@ -1775,6 +2132,23 @@ hipError_t group_sort_reduce(hipStream_t s, const uint64_t *in_k, const uint64_t
     hipError_t e = group_sort_u64(s, in_k, in_v, n, 0, nullptr, 1, &pk, ws, &sk, &sv);
     if (e != hipSuccess) return e;
     return seg_reduce(s, sk, sv, n, op, out_k, out_v, h_nout, ws, false, pk != 0);
+}
+
+hipError_t group_rows(hipStream_t s, const uint64_t *in_k, const uint64_t *in_v, uint64_t n,
+                      int route, uint64_t *out_k, uint64_t *out_v, Ws &ws, int *route_taken) {
+    if (route_taken) *route_taken = 0;
+    if (n == 0) return hipSuccess;
+    const uint64_t *sk, *sv;
+    int pk = 0;
+    HIP_TRY(group_sort_u64(s, in_k, in_v, n, 0, nullptr, 1, &pk, ws, &sk, &sv, route, route_taken));
+    if (pk) {
+        uint32_t nb = nblocks_for(n);
+        hipLaunchKernelGGL(k_unpack_rows, dim3(nb < 2048 ? nb : 2048), dim3(BLOCK), 0, s,
+                           sk, n, out_k, out_v);
+        return hipGetLastError();
+    }
+    HIP_TRY(hipMemcpyAsync(out_k, sk, n * 8, hipMemcpyDeviceToDevice, s));
+    return hipMemcpyAsync(out_v, sv, n * 8, hipMemcpyDeviceToDevice, s);
 }
 
 /* ------------------------------------------------------------------ */

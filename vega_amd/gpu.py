@@ -591,6 +591,29 @@ def dev_sort_stats(keys_t, vals_t, out_k, out_count, out_sum, out_min, out_max, 
     return nout.value
 
 
+def dev_group_rows(keys_t, vals_t, route, out_k, out_v, ws_t):
+    """diagnostic: the grouped rows dev_sort_reduce aggregates, as SoA columns.
+    route 0 automatic, 1 four hash passes + cleanup, 2 three passes + bucket
+    finish; returns the route that produced the result"""
+    taken = ctypes.c_int(0)
+    _check(lib().vega_dev_group_rows_i64(
+        _stream(), _t(keys_t), _t(vals_t), ctypes.c_uint64(keys_t.numel()),
+        ctypes.c_int(route), _t(out_k), _t(out_v), _t(ws_t),
+        ctypes.c_size_t(ws_t.numel()), ctypes.byref(taken)), "dev_group_rows")
+    return taken.value
+
+
+def diag_bucket_rows(sample_keys, n):
+    """rows per occupied hash bucket the automatic route would estimate for n
+    rows from these (<= 2048, host) sampled keys; no device call"""
+    k = _np(sample_keys)
+    out = ctypes.c_double(0)
+    _check(lib().vega_diag_bucket_rows(_pp(k), ctypes.c_uint32(len(k)),
+                                       ctypes.c_uint64(n), ctypes.byref(out)),
+           "diag_bucket_rows")
+    return out.value
+
+
 def dev_sort_pairs(keys_t, vals_t, ws_t):
     n = keys_t.numel()
     _check(lib().vega_dev_sort_pairs_i64(_stream(), _t(keys_t), _t(vals_t),
