@@ -66,7 +66,13 @@ hipError_t group_sort_u64(hipStream_t s, const uint64_t *in_k, const uint64_t *i
                           uint64_t n, int force_hbytes, int *order_tag,
                           int want_packed, int *out_packed, Ws &ws,
                           const uint64_t **res_k, const uint64_t **res_v,
-                          int route = 0, int *route_taken = nullptr);
+                          int route = 0, int *route_taken = nullptr,
+                          const uint32_t **fin_heads = nullptr);
+/* *fin_heads (optional out): run-head counts per 2048-row tile that the bucket
+ * finish kept while it stored the rows, for seg_reduce / seg_stats — non-null
+ * only when the finish route produced the result (not after its error flag,
+ * not on the four-pass route, narrow keys, joins or cogroup). The buffer is
+ * carved from ws and is consumed (scanned in place) by its one user. */
 
 /* rows per occupied hash bucket that group_sort_u64's automatic route
  * estimates from its key sample (host arithmetic only; ns <= 2048) */
@@ -79,13 +85,15 @@ hipError_t group_rows(hipStream_t s, const uint64_t *in_k, const uint64_t *in_v,
                       int route, uint64_t *out_k, uint64_t *out_v, Ws &ws, int *route_taken);
 
 /* segmented aggregate over key-sorted rows: one output row per equal-key
- * run. op: VEGA_OP_*. Returns #segments in *h_nout (after stream sync). */
+ * run. op: VEGA_OP_*. Returns #segments in *h_nout (after stream sync).
+ * out_k / out_v need no initialising: every slot is plain-stored.
+ * fin_heads: group_sort_u64's per-tile head counts, or nullptr to count. */
 hipError_t seg_reduce(hipStream_t s, const uint64_t *k, const void *v, uint64_t n,
                       int op, uint64_t *out_k, void *out_v, uint64_t *h_nout, Ws &ws,
-                      bool v_prezeroed = false, bool packed = false);
+                      bool packed = false, const uint32_t *fin_heads = nullptr);
 
-/* grouping sort + segmented aggregate, accumulator init overlapped on a
- * side stream (the fast path reduce_by_key / group_count use) */
+/* grouping sort + segmented aggregate (the fast path reduce_by_key /
+ * group_count use) */
 hipError_t group_sort_reduce(hipStream_t s, const uint64_t *in_k, const uint64_t *in_v,
                              uint64_t n, int op, uint64_t *out_k, void *out_v,
                              uint64_t *h_nout, Ws &ws);
@@ -97,7 +105,7 @@ hipError_t group_sort_reduce(hipStream_t s, const uint64_t *in_k, const uint64_t
 hipError_t seg_stats(hipStream_t s, const uint64_t *k, const uint64_t *v, uint64_t n,
                      int64_t *out_k, int64_t *out_count, int64_t *out_sum,
                      int64_t *out_min, int64_t *out_max, uint64_t *h_nout, Ws &ws,
-                     bool packed = false);
+                     bool packed = false, const uint32_t *fin_heads = nullptr);
 
 /* grouping sort (as group_sort_reduce runs it) + seg_stats */
 hipError_t group_sort_stats(hipStream_t s, const uint64_t *in_k, const uint64_t *in_v,

@@ -1292,6 +1292,10 @@ __global__ void k_group_cleanup_long(const uint64_t *k, const uint32_t *h32,
  * applies k_group_cleanup's relaxed rule to each equal-h32 run, and stores
  * the rows whose final position lies in its own tile. Buckets across a tile
  * edge are computed for both tiles, identically; each row is stored once.
+ * While it stores its tile's rows the block also counts the run heads among
+ * them (a key differing from the row before, whose final position it knows
+ * too) and plain-stores the count to fin_heads[tile]: seg_reduce's per-tile
+ * head counts, without another pass over the rows.
  * Blocks share only *err: it is set when a bucket does not close inside the
  * slack, holds more than FIN_BUCKET_CAP rows, or a dirty run exceeds 64
  * rows, and the caller then runs the four-pass route from the untouched
@@ -1374,13 +1378,15 @@ __device__ __forceinline__ void fin_fix_run(const ulonglong2 *s_row, uint16_t *s
 }
 
 __global__ __launch_bounds__(FIN_B) void k_bucket_finish(const uint64_t *in, uint64_t *out,
-                                                         uint64_t n, int *err) {
+                                                         uint64_t n, int *err,
+                                                         uint32_t *fin_heads) {
     __shared__ ulonglong2 s_row[FIN_SPAN]; /* staged rows, input order */
     __shared__ uint32_t s_h[FIN_SPAN];     /* h32 per staged row */
     __shared__ uint16_t s_src[FIN_SPAN];   /* final position -> staged row */
     __shared__ uint16_t s_bk[FIN_SPAN];    /* first row of each bucket in the span */
     __shared__ __attribute__((aligned(16))) uint32_t s_cnt[FIN_B / 64][256]; /* per wave */
     __shared__ int s_lo, s_hi, s_bad, s_nbk;
+    __shared__ uint32_t s_heads[FIN_B / 64]; /* run heads each wave stored this tile */
 
     const uint32_t ntiles = (uint32_t)((n + FIN_FT - 1) / FIN_FT);
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -1514,14 +1520,50 @@ __global__ __launch_bounds__(FIN_B) void k_bucket_finish(const uint64_t *in, uin
         __syncthreads();
         const uint32_t next = tile + gridDim.x;
         if (next < ntiles) fetch(next);
-        if (order_tile(g0, m, a0, a1)) {
+        const bool done = order_tile(g0, m, a0, a1);
+        if (done) {
+            /* the stored rows are final, and so is s_src[p - 1] for p > lo
+             * (the buckets meeting the tile are ordered whole): a row is a
+             * run head when its key differs from the row before. Position lo
+             * is one by construction — global row 0, or the row before lies
+             * in another bucket and so has another key. Every lane reads the
+             * previous key itself, next to its own row (clamped indices, no
+             * branch): two dependent LDS round trips for all the rounds
+             * together. Taking it from the lane below, with lane 0 reading
+             * LDS, chains five per round: 0.15 ms slower at 1e9 rows. */
+            const int lo = s_lo;
+            uint32_t heads = 0;
+            uint16_t si[FIN_FT / FIN_B], sp[FIN_FT / FIN_B];
 #pragma unroll
             for (int q = 0; q < FIN_FT / FIN_B; ++q) {
-                int p = a0 + q * FIN_B + threadIdx.x;
-                if (p < a1) ((ulonglong2 *)out)[g0 + p] = s_row[s_src[p]];
+                const int p = a0 + q * FIN_B + threadIdx.x;
+                const int pc = p < a1 ? p : a1 - 1;
+                si[q] = s_src[pc];
+                sp[q] = s_src[pc > lo ? pc - 1 : pc];
             }
+            ulonglong2 row[FIN_FT / FIN_B];
+            uint64_t pkey[FIN_FT / FIN_B];
+#pragma unroll
+            for (int q = 0; q < FIN_FT / FIN_B; ++q) {
+                row[q] = s_row[si[q]];
+                pkey[q] = s_row[sp[q]].x;
+            }
+#pragma unroll
+            for (int q = 0; q < FIN_FT / FIN_B; ++q) {
+                const int p = a0 + q * FIN_B + threadIdx.x;
+                if (p < a1) ((ulonglong2 *)out)[g0 + p] = row[q];
+                const bool head = p < a1 && (p == lo || row[q].x != pkey[q]);
+                heads += (uint32_t)__popcll(__ballot(head));
+            }
+            if (lane == 0) s_heads[w] = heads;
         }
         __syncthreads(); /* LDS is restaged next */
+        if (done && threadIdx.x == 0) {
+            uint32_t t = 0;
+#pragma unroll
+            for (int i = 0; i < FIN_B / 64; ++i) t += s_heads[i];
+            fin_heads[tile] = t;
+        }
         tile = next;
     }
 }
@@ -1553,17 +1595,23 @@ __global__ void k_unpack_rows(const uint64_t *pk, uint64_t n, uint64_t *k, uint6
  *     strategy with them (diagnostic entry only).
  * *route_taken (optional): 1 or 2 for the route that produced the result —
  * 1 also when the finish raised its flag and the four passes ran after it —
- * 0 when no hash route did (n <= 1, narrow keys). */
+ * 0 when no hash route did (n <= 1, narrow keys).
+ * *fin_heads (optional): k_bucket_finish's run-head count per FIN_FT-row
+ * tile, ceil(n / FIN_FT) entries at the front of a buffer of 2 * nb + 1 (the
+ * shape seg_reduce scans). Set only when the finish produced the result; on
+ * every other route, and after the finish's flag (some tiles then hold no
+ * count), it is nullptr and the caller counts heads itself. */
 hipError_t group_sort_u64(hipStream_t s, const uint64_t *in_k, const uint64_t *in_v,
                           uint64_t n, int force_hbytes, int *order_tag,
                           int want_packed, int *out_packed, Ws &ws,
                           const uint64_t **res_k, const uint64_t **res_v,
-                          int route, int *route_taken) {
+                          int route, int *route_taken, const uint32_t **fin_heads) {
     *res_k = in_k;
     *res_v = in_v;
     if (out_packed) *out_packed = 0;
     if (order_tag) *order_tag = 0;
     if (route_taken) *route_taken = 0;
+    if (fin_heads) *fin_heads = nullptr;
     if (n <= 1) return hipSuccess;
     if (n >= (1ULL << 32)) return hipErrorNotSupported; /* u32 hist/scan limit (vega_gpu.h) */
     uint32_t nb = nblocks_for(n);
@@ -1582,8 +1630,11 @@ hipError_t group_sort_u64(hipStream_t s, const uint64_t *in_k, const uint64_t *i
     uint32_t *h32buf = (uint32_t *)ws.take(n * 4);
     unsigned long long *wl = (unsigned long long *)ws.take(CLEANUP_WL_CAP * 8);
     uint32_t *wl_count = (uint32_t *)ws.take(256);
+    /* run heads per finish tile, padded to the 2 * nb + 1 entries seg_reduce
+     * scans in place; taken here so that it outlives the sort */
+    uint32_t *fh_d = (uint32_t *)ws.take(((size_t)2 * nb + 1) * 4);
     if (!pA || !pB || !desc || !gbase_d || !ticket || !h8 || !d_err || !d_abort ||
-        !ff_d || !h32buf || !wl || !wl_count)
+        !ff_d || !h32buf || !wl || !wl_count || !fh_d)
         return hipErrorOutOfMemory;
     HIP_TRY(hipMemsetAsync(d_abort, 0, 4, s));
     HIP_TRY(hipMemsetAsync(desc, 0, (size_t)nb * 256 * 8, s));
@@ -1700,7 +1751,7 @@ hipError_t group_sort_u64(hipStream_t s, const uint64_t *in_k, const uint64_t *i
             ProfScope pk("bucket_finish", s);
             const uint32_t ntiles = (uint32_t)((n + FIN_FT - 1) / FIN_FT);
             hipLaunchKernelGGL(k_bucket_finish, dim3(ntiles < FIN_GRID ? ntiles : FIN_GRID),
-                               dim3(FIN_B), 0, s, cur_k, pB, n, d_err);
+                               dim3(FIN_B), 0, s, cur_k, pB, n, d_err, fh_d);
             HIP_TRY(hipGetLastError());
         }
         int fl[2] = {0, 0};
@@ -1711,6 +1762,7 @@ hipError_t group_sort_u64(hipStream_t s, const uint64_t *in_k, const uint64_t *i
         if (!fl[0]) {
             if (out_packed) *out_packed = 1;
             if (route_taken) *route_taken = 2;
+            if (fin_heads) *fin_heads = fh_d; /* every tile stored its count */
             *res_k = pB;
             *res_v = nullptr;
             return hipSuccess;
@@ -1805,13 +1857,23 @@ __global__ void k_head_count(const uint64_t *k, uint64_t n, uint32_t *hc) {
  * unrolled sequential loads vectorize and every 64 B line is fully consumed
  * by exactly one lane, so the pattern is bandwidth-clean and occupancy is
  * not LDS-bound. */
-/* OP==2 (SUM_F64) is DETERMINISTIC: no atomics anywhere. Interior runs are
- * stored exclusively by the chunk that starts them; each chunk's leading
- * partial (the part of the run open at its start) goes to
- * (lead_seg, lead_part)[chunk], and k_f64_seg_combine folds those in chunk
- * order — a fixed summation shape for a given n, so results are bit-stable
- * run to run (and within 1e-6 rel of the reference's sequential merge,
- * pair_rdd.rs:74-78). */
+/* Store discipline, every op: no atomics in this kernel, and no slot of
+ * out_k / out_v needs initialising. The chunk that holds a run's head
+ * plain-stores the run's key and the value accumulated inside that chunk
+ * (interior runs are complete; the last run started in the chunk stores what
+ * it has so far). The rows before a chunk's first head — the part of the run
+ * open at its start, the whole chunk if it has no head — are its "lead" and go
+ * to (lead_seg, lead_part)[chunk]; lead_seg is written for every chunk
+ * (0xFFFFFFFF: none). A second small kernel on the same stream folds the
+ * leads into the slots: k_seg_lead_fold for the integer ops (exact in any
+ * order), k_f64_seg_combine for OP 2.
+ * head_base[blockIdx.x * hstride] is the tile's first segment id: hstride 1
+ * for scanned k_head_count output, 2 for scanned k_bucket_finish counts (two
+ * finish tiles per tile here).
+ * OP==2 (SUM_F64) is DETERMINISTIC: k_f64_seg_combine folds the leads in
+ * chunk order — a fixed summation shape for a given n, so results are
+ * bit-stable run to run (and within 1e-6 rel of the reference's sequential
+ * merge, pair_rdd.rs:74-78). */
 /* 512 threads x 8-row chunks per 4096-row tile: shorter per-thread load
  * chains than 256x16 (the chunk loads are the latency chain) */
 #define SEG_B 512
@@ -1819,9 +1881,9 @@ __global__ void k_head_count(const uint64_t *k, uint64_t n, uint32_t *hc) {
 template <int OP, bool PK>
 __global__ __launch_bounds__(SEG_B) void k_seg_emit(
     const uint64_t *__restrict__ k, const void *__restrict__ vv, uint64_t n,
-    const uint32_t *__restrict__ head_base, int64_t *__restrict__ out_k,
-    void *__restrict__ out_vv, uint32_t *__restrict__ lead_seg,
-    double *__restrict__ lead_part) {
+    const uint32_t *__restrict__ head_base, uint32_t hstride,
+    int64_t *__restrict__ out_k, void *__restrict__ out_vv,
+    uint32_t *__restrict__ lead_seg, double *__restrict__ lead_part) {
     __shared__ uint32_t wsc[SEG_B / 64];
     constexpr bool NEED_V = (OP != 1);
 
@@ -1888,7 +1950,7 @@ __global__ __launch_bounds__(SEG_B) void k_seg_emit(
 
     if (OP == 2) { /* deterministic f64 path (see kernel comment) */
         uint64_t chunk_id = (uint64_t)blockIdx.x * SEG_B + t;
-        int64_t sid = (int64_t)head_base[blockIdx.x] + excl - 1; /* run open at chunk start */
+        int64_t sid = (int64_t)head_base[(size_t)blockIdx.x * hstride] + excl - 1; /* run open at chunk start */
         if (c0g >= n) {
             lead_seg[chunk_id] = 0xFFFFFFFFu;
             return;
@@ -1928,19 +1990,24 @@ __global__ __launch_bounds__(SEG_B) void k_seg_emit(
         return;
     }
 
-    /* Fast path: a fully-distinct interior chunk whose last run does not
-     * continue into the next chunk (the dominant C1 shape) emits its 16
-     * length-1 runs with pure vector stores — no branches, no atomics. */
-    bool fast = false;
-    if (cnt == SEG_IPT && c0g + SEG_IPT <= n) {
-        uint64_t nk = (c0g + SEG_IPT < n) ? k[PK ? 2 * (c0g + SEG_IPT) : c0g + SEG_IPT] : ~kk[SEG_IPT - 1];
-        fast = (nk != kk[SEG_IPT - 1]);
+    /* Integer ops: the f64 store discipline with exact accumulators. */
+    const uint64_t chunk_id = (uint64_t)blockIdx.x * SEG_B + t;
+    if (c0g >= n) {
+        lead_seg[chunk_id] = 0xFFFFFFFFu;
+        return;
     }
-    int64_t segid = (int64_t)head_base[blockIdx.x] + excl - 1;
-    int64_t acc_i = (OP == 3) ? INT64_MAX : (OP == 4) ? INT64_MIN : 0;
-    double acc_f = 0.0;
-    bool have = false, started_here = false;
-    if (fast) {
+    constexpr int64_t IDENT = (OP == 3) ? INT64_MAX : (OP == 4) ? INT64_MIN : 0;
+    auto fold = [](int64_t a, uint64_t x) -> int64_t {
+        if (OP == 0) return (int64_t)((uint64_t)a + x);
+        if (OP == 1) return a + 1;
+        if (OP == 3) return (int64_t)x < a ? (int64_t)x : a;
+        return (int64_t)x > a ? (int64_t)x : a;
+    };
+    int64_t segid = (int64_t)head_base[(size_t)blockIdx.x * hstride] + excl - 1; /* run open at chunk start */
+    /* Fast path: a fully-distinct interior chunk (the dominant C1 shape)
+     * emits its length-1 runs with pure vector stores — no branches. If its
+     * last run goes on, the next chunk's lead carries the rest. */
+    if (cnt == SEG_IPT && c0g + SEG_IPT <= n) {
         int64_t s0 = segid + 1;
         int64_t *okp = (int64_t *)out_k + s0;
         uint64_t *ovp = (uint64_t *)out_vv + s0;
@@ -1960,68 +2027,88 @@ __global__ __launch_bounds__(SEG_B) void k_seg_emit(
                 ovp[j] = (OP == 1) ? 1ULL : sv[j];
             }
         }
-        /* have stays false: the wave tail-combine below is inert for this
-         * lane but still participates in the shfl lanes */
-    } else
+        lead_seg[chunk_id] = 0xFFFFFFFFu;
+        return;
+    }
+    const int64_t open_seg = segid;
+    int64_t lead = IDENT, acc = IDENT;
+    bool seen = false; /* a head has been met: acc belongs to a run started here */
 #pragma unroll
     for (int j = 0; j < SEG_IPT; ++j) {
         uint64_t gi = c0g + j;
-        if (gi >= n) break;
-        uint64_t key = kk[j];
-        uint64_t pk = (j > 0) ? kk[j - 1] : prev;
-        bool head = (gi == 0) || (key != pk);
-        if (head) {
-            if (have) { /* previous run terminated by this head */
-                if (started_here) { /* exclusive: plain store */
-                    if (OP == 2) ((double *)out_vv)[segid] = acc_f;
-                    else ((int64_t *)out_vv)[segid] = acc_i;
-                } else {
-                    if (OP == 0 || OP == 1) atomicAdd((unsigned long long *)((int64_t *)out_vv + segid), (unsigned long long)acc_i);
-                    else if (OP == 2) atomicAdd((double *)out_vv + segid, acc_f);
-                    else if (OP == 3) atomicMin((long long *)((int64_t *)out_vv + segid), (long long)acc_i);
-                    else atomicMax((long long *)((int64_t *)out_vv + segid), (long long)acc_i);
+        if (gi < n) {
+            uint64_t pk = (j > 0) ? kk[j - 1] : prev;
+            if (gi == 0 || kk[j] != pk) {
+                if (seen) ((int64_t *)out_vv)[segid] = acc; /* interior run: complete */
+                segid++;
+                out_k[segid] = (int64_t)kk[j];
+                acc = IDENT;
+                seen = true;
+            }
+            if (seen) acc = fold(acc, sv[j]);
+            else lead = fold(lead, sv[j]);
+        }
+    }
+    /* last run started here: what it has so far; k_seg_lead_fold adds the
+     * leads of the chunks it runs on into */
+    if (seen) ((int64_t *)out_vv)[segid] = acc;
+    /* row c0g is valid: it is either a head (cnt counts it first) or the lead */
+    if (c0g != 0 && kk[0] == prev) {
+        lead_seg[chunk_id] = (uint32_t)open_seg;
+        ((int64_t *)lead_part)[chunk_id] = lead;
+    } else {
+        lead_seg[chunk_id] = 0xFFFFFFFFu;
+    }
+}
+
+/* Integer ops: fold every chunk's lead into its run's slot, which already
+ * holds what the chunk with the run's head stored (stream order). The chunks
+ * whose leads belong to one run are consecutive, so equal lead_seg values are
+ * first combined within the wave (segmented inclusive shuffle scan) and the
+ * last lane of each group issues one atomic: a hot key spanning millions of
+ * chunks costs one atomic per wave, and nothing walks serially. Integer sum,
+ * count, min and max are exact in any order. */
+constexpr int SEG_FOLD_U = 4; /* independent lead_seg loads in flight per thread */
+template <int OP>
+__global__ __launch_bounds__(BLOCK) void k_seg_lead_fold(
+    const uint32_t *__restrict__ lead_seg, const int64_t *__restrict__ lead_part,
+    uint64_t nchunks, int64_t *__restrict__ out_v) {
+    const int lane = threadIdx.x & 63;
+    constexpr int U = SEG_FOLD_U;
+    const uint64_t stride = (uint64_t)gridDim.x * BLOCK * U;
+    /* block-uniform trip count: every lane takes part in the shuffles */
+    for (uint64_t c0 = (uint64_t)blockIdx.x * BLOCK * U; c0 < nchunks; c0 += stride) {
+        uint32_t sgs[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const uint64_t c = c0 + (uint64_t)u * BLOCK + threadIdx.x;
+            sgs[u] = (c < nchunks) ? lead_seg[c] : 0xFFFFFFFFu;
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const uint64_t c = c0 + (uint64_t)u * BLOCK + threadIdx.x;
+            const uint32_t sg = sgs[u];
+            const bool have = sg != 0xFFFFFFFFu;
+            if (!__any(have)) continue;
+            int64_t acc = have ? lead_part[c] : 0;
+            long long sid = have ? (long long)sg : -(long long)(lane + 2);
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1) {
+                long long s2 = __shfl_up(sid, off);
+                long long a2 = __shfl_up((long long)acc, off);
+                if (lane >= off && s2 == sid) {
+                    if (OP == 3) acc = (int64_t)a2 < acc ? (int64_t)a2 : acc;
+                    else if (OP == 4) acc = (int64_t)a2 > acc ? (int64_t)a2 : acc;
+                    else acc = (int64_t)((uint64_t)acc + (uint64_t)a2);
                 }
             }
-            segid++;
-            out_k[segid] = (int64_t)key;
-            acc_i = (OP == 3) ? INT64_MAX : (OP == 4) ? INT64_MIN : 0;
-            acc_f = 0.0;
-            started_here = true;
-        }
-        have = true;
-        if (OP == 0) acc_i = (int64_t)((uint64_t)acc_i + sv[j]);
-        else if (OP == 1) acc_i += 1;
-        else if (OP == 2) acc_f += __longlong_as_double((long long)sv[j]);
-        else if (OP == 3) { int64_t x = (int64_t)sv[j]; acc_i = x < acc_i ? x : acc_i; }
-        else { int64_t x = (int64_t)sv[j]; acc_i = x > acc_i ? x : acc_i; }
-    }
-    /* Tail flush. A long (hot-key) run makes MANY consecutive chunks
-     * head-free, all flushing into the same segid — combine those within
-     * the wave first (segmented inclusive shfl-scan over the ascending,
-     * contiguous equal-segid lanes; one atomic per group instead of 64). */
-    long long sid = (have && cnt == 0) ? (long long)segid : -(long long)(lane + 2);
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        long long s2 = __shfl_up(sid, off);
-        if (OP == 2) {
-            double a2 = __shfl_up(acc_f, off);
-            if (lane >= off && s2 == sid) acc_f += a2;
-        } else {
-            long long a2 = __shfl_up((long long)acc_i, off);
-            if (lane >= off && s2 == sid) {
-                if (OP == 3) acc_i = (int64_t)a2 < acc_i ? (int64_t)a2 : acc_i;
-                else if (OP == 4) acc_i = (int64_t)a2 > acc_i ? (int64_t)a2 : acc_i;
-                else acc_i = (int64_t)((uint64_t)acc_i + (uint64_t)a2);
+            long long snext = __shfl_down(sid, 1);
+            if (have && (lane == 63 || snext != sid)) {
+                if (OP == 0 || OP == 1) atomicAdd((unsigned long long *)(out_v + sg), (unsigned long long)acc);
+                else if (OP == 3) atomicMin((long long *)(out_v + sg), (long long)acc);
+                else atomicMax((long long *)(out_v + sg), (long long)acc);
             }
         }
-    }
-    long long snext = __shfl_down(sid, 1);
-    bool lastg = (lane == 63) || (snext != sid);
-    if (have && (cnt != 0 || lastg)) {
-        if (OP == 0 || OP == 1) atomicAdd((unsigned long long *)((int64_t *)out_vv + segid), (unsigned long long)acc_i);
-        else if (OP == 2) atomicAdd((double *)out_vv + segid, acc_f);
-        else if (OP == 3) atomicMin((long long *)((int64_t *)out_vv + segid), (long long)acc_i);
-        else atomicMax((long long *)((int64_t *)out_vv + segid), (long long)acc_i);
     }
 }
 
@@ -2043,55 +2130,74 @@ __global__ void k_f64_seg_combine(const uint32_t *lead_seg, const double *lead_p
     }
 }
 
-hipError_t seg_reduce(hipStream_t s, const uint64_t *k, const void *v, uint64_t n,
-                      int op, uint64_t *out_k, void *out_v, uint64_t *h_nout, Ws &ws,
-                      bool v_prezeroed, bool packed) {
-    if (n == 0) { *h_nout = 0; return hipSuccess; }
-    if (n >= (1ULL << 32)) return hipErrorNotSupported; /* u32 head scan limit */
-    uint32_t nb = nblocks_for(n);
-    uint32_t *hc = (uint32_t *)ws.take(((size_t)nb + 1) * 4);
-    if (!hc) return hipErrorOutOfMemory;
-    uint64_t nchunks = (uint64_t)nb * 512; /* SEG_B chunks per tile */
-    uint32_t *lead_seg = nullptr;
-    double *lead_part = nullptr;
-    if (op == 2) {
-        lead_seg = (uint32_t *)ws.take(nchunks * 4);
-        lead_part = (double *)ws.take(nchunks * 8);
-        if (!lead_seg || !lead_part) return hipErrorOutOfMemory;
-    }
-    {
-        ProfScope ps("head_count", s);
+/* First segment id of every TILE-row tile, for k_seg_emit / k_seg_stats:
+ * *hc_out[b * *hstride] for tile b, the segment total behind the last tile
+ * at *total_d. Per-tile head counts come from k_head_count (hstride 1), or,
+ * when group_sort_u64 handed over k_bucket_finish's counts per FIN_FT-row
+ * tile (fin_heads, 2 * nb + 1 entries, scanned in place), from those: two
+ * finish tiles per tile, hstride 2, no pass over the rows. The "head_count"
+ * scope covers the counts, however obtained, and their scan. */
+static_assert(TILE == 2 * FIN_FT, "two finish tiles per segmented-reduce tile");
+static hipError_t seg_head_bases(hipStream_t s, const uint64_t *k, uint64_t n, bool packed,
+                                 const uint32_t *fin_heads, Ws &ws, const uint32_t **hc_out,
+                                 uint32_t *hstride, const uint32_t **total_d) {
+    const uint32_t nb = nblocks_for(n);
+    ProfScope ps("head_count", s);
+    uint32_t *hc;
+    uint64_t nent; /* counts to scan, without the total's slot */
+    if (fin_heads) {
+        hc = const_cast<uint32_t *>(fin_heads);
+        nent = (uint64_t)2 * nb;
+        *hstride = 2;
+        /* ceil(n / FIN_FT) may be odd: the entry behind the last finish tile
+         * counts nothing; then the slot the scan leaves the total in */
+        const uint64_t nfin = (n + FIN_FT - 1) / FIN_FT;
+        HIP_TRY(hipMemsetAsync(hc + nfin, 0, (size_t)(nent + 1 - nfin) * 4, s));
+    } else {
+        hc = (uint32_t *)ws.take(((size_t)nb + 1) * 4);
+        if (!hc) return hipErrorOutOfMemory;
+        nent = nb;
+        *hstride = 1;
         if (packed)
             hipLaunchKernelGGL((k_head_count<true>), dim3(nb), dim3(BLOCK), 0, s, k, n, hc);
         else
             hipLaunchKernelGGL((k_head_count<false>), dim3(nb), dim3(BLOCK), 0, s, k, n, hc);
         HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemsetAsync(hc + nb, 0, 4, s));
     }
-    HIP_TRY(hipMemsetAsync(hc + nb, 0, 4, s));
     {
         Ws w2 = ws;
-        HIP_TRY(scan_u32_excl(s, hc, (uint64_t)nb + 1, w2));
+        HIP_TRY(scan_u32_excl(s, hc, nent + 1, w2));
     }
-    uint32_t total = 0;
-    HIP_TRY(hipMemcpyAsync(&total, hc + nb, 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
+    *hc_out = hc;
+    *total_d = hc + nent;
+    return hipSuccess;
+}
 
-    /* init output accumulators (skipped when the caller pre-initialized
-     * them overlapped with the sort, or for f64 — every f64 slot gets a
-     * plain store from its run's starting chunk) */
-    if (!v_prezeroed && op != 2) {
-        if (op == 3 || op == 4) {
-            hipLaunchKernelGGL(k_fill_i64, dim3(2048), dim3(BLOCK), 0, s,
-                               (int64_t *)out_v, (uint64_t)total, op == 3 ? INT64_MAX : INT64_MIN);
-            HIP_TRY(hipGetLastError());
-        } else {
-            HIP_TRY(hipMemsetAsync(out_v, 0, (size_t)total * 8, s));
-        }
-    }
+/* No accumulator init, for any op: k_seg_emit plain-stores every slot and the
+ * fold kernel behind it (same stream) adds the leads — see k_seg_emit. The
+ * host therefore needs the segment total only for *h_nout, and waits for the
+ * stream once, after the last launch. fin_heads: see seg_head_bases. */
+hipError_t seg_reduce(hipStream_t s, const uint64_t *k, const void *v, uint64_t n,
+                      int op, uint64_t *out_k, void *out_v, uint64_t *h_nout, Ws &ws,
+                      bool packed, const uint32_t *fin_heads) {
+    if (n == 0) { *h_nout = 0; return hipSuccess; }
+    if (n >= (1ULL << 32)) return hipErrorNotSupported; /* u32 head scan limit */
+    if (op < 0 || op > 4) return hipErrorInvalidValue;
+    uint32_t nb = nblocks_for(n);
+    uint64_t nchunks = (uint64_t)nb * SEG_B;
+    uint32_t *lead_seg = (uint32_t *)ws.take(nchunks * 4);
+    double *lead_part = (double *)ws.take(nchunks * 8);
+    if (!lead_seg || !lead_part) return hipErrorOutOfMemory;
+    const uint32_t *hc, *total_d;
+    uint32_t hstride;
+    HIP_TRY(seg_head_bases(s, k, n, packed, fin_heads, ws, &hc, &hstride, &total_d));
+    uint32_t total = 0;
+    HIP_TRY(hipMemcpyAsync(&total, total_d, 4, hipMemcpyDeviceToHost, s));
     {
         ProfScope ps("seg_emit", s);
         size_t sh = 0;
-#define SEG_LAUNCH(OPN, PKB) hipLaunchKernelGGL((k_seg_emit<OPN, PKB>), dim3(nb), dim3(512), sh, s, k, v, n, hc, (int64_t *)out_k, out_v, lead_seg, lead_part)
+#define SEG_LAUNCH(OPN, PKB) hipLaunchKernelGGL((k_seg_emit<OPN, PKB>), dim3(nb), dim3(SEG_B), sh, s, k, v, n, hc, hstride, (int64_t *)out_k, out_v, lead_seg, lead_part)
         switch (op * 2 + (packed ? 1 : 0)) {
         case 0: SEG_LAUNCH(0, false); break;
         case 1: SEG_LAUNCH(0, true); break;
@@ -2114,24 +2220,47 @@ hipError_t seg_reduce(hipStream_t s, const uint64_t *k, const void *v, uint64_t 
         hipLaunchKernelGGL(k_f64_seg_combine, dim3(gb), dim3(BLOCK), 0, s,
                            lead_seg, lead_part, nchunks, (double *)out_v);
         HIP_TRY(hipGetLastError());
+    } else {
+        ProfScope ps("seg_fold", s);
+        const uint64_t per = (uint64_t)BLOCK * SEG_FOLD_U; /* chunks per block and round */
+        const uint64_t rounds = (nchunks + per - 1) / per;
+        uint32_t gb = (uint32_t)(rounds < 4096 ? rounds : 4096); /* grid-stride beyond */
+        const int64_t *lp = (const int64_t *)lead_part;
+        switch (op) {
+        case 0:
+        case 1:
+            hipLaunchKernelGGL((k_seg_lead_fold<0>), dim3(gb), dim3(BLOCK), 0, s, lead_seg, lp,
+                               nchunks, (int64_t *)out_v);
+            break;
+        case 3:
+            hipLaunchKernelGGL((k_seg_lead_fold<3>), dim3(gb), dim3(BLOCK), 0, s, lead_seg, lp,
+                               nchunks, (int64_t *)out_v);
+            break;
+        default:
+            hipLaunchKernelGGL((k_seg_lead_fold<4>), dim3(gb), dim3(BLOCK), 0, s, lead_seg, lp,
+                               nchunks, (int64_t *)out_v);
+            break;
+        }
+        HIP_TRY(hipGetLastError());
     }
+    HIP_TRY(hipStreamSynchronize(s));
     *h_nout = total;
     return hipSuccess;
 }
 
-/* grouping sort + segmented aggregate. (Overlapping the accumulator init
- * with the sort on a side stream was measured a wash — the sort is itself
- * HBM-bound, so the init just steals its bandwidth; f64 still skips the
- * init entirely since its deterministic path plain-stores every slot.) */
+/* grouping sort + segmented aggregate; on the finish route the sort hands its
+ * per-tile head counts over and the rows are not read again to count them */
 hipError_t group_sort_reduce(hipStream_t s, const uint64_t *in_k, const uint64_t *in_v,
                              uint64_t n, int op, uint64_t *out_k, void *out_v,
                              uint64_t *h_nout, Ws &ws) {
     if (n == 0) { *h_nout = 0; return hipSuccess; }
     const uint64_t *sk, *sv;
     int pk = 0;
-    hipError_t e = group_sort_u64(s, in_k, in_v, n, 0, nullptr, 1, &pk, ws, &sk, &sv);
+    const uint32_t *fh = nullptr;
+    hipError_t e = group_sort_u64(s, in_k, in_v, n, 0, nullptr, 1, &pk, ws, &sk, &sv, 0,
+                                  nullptr, &fh);
     if (e != hipSuccess) return e;
-    return seg_reduce(s, sk, sv, n, op, out_k, out_v, h_nout, ws, false, pk != 0);
+    return seg_reduce(s, sk, sv, n, op, out_k, out_v, h_nout, ws, pk != 0, fh);
 }
 
 hipError_t group_rows(hipStream_t s, const uint64_t *in_k, const uint64_t *in_v, uint64_t n,
@@ -2169,7 +2298,9 @@ struct StatsAcc {
 
 /* Sibling of k_seg_emit<OP,PK> for i64 values: same geometry (SEG_B threads x
  * SEG_IPT-row chunks, register-only, 16-B loads), same block-exclusive head
- * scan seeded from head_base[blockIdx.x], same store / atomic discipline —
+ * scan seeded from head_base[blockIdx.x * hstride] — but its own store
+ * discipline: runs contained in a chunk are plain-stored, a run open at a
+ * chunk start and every chunk's last run are flushed with global atomics —
  * with four accumulators per run and five SoA outputs. All four fields are
  * integer, so any flush order gives the same bits: atomics are the only
  * inter-block traffic, nothing waits on another block. out_count / out_sum
@@ -2177,7 +2308,8 @@ struct StatsAcc {
 template <bool PK>
 __global__ __launch_bounds__(SEG_B) void k_seg_stats(
     const uint64_t *__restrict__ k, const uint64_t *__restrict__ v, uint64_t n,
-    const uint32_t *__restrict__ head_base, int64_t *__restrict__ out_k,
+    const uint32_t *__restrict__ head_base, uint32_t hstride,
+    int64_t *__restrict__ out_k,
     int64_t *__restrict__ out_count, int64_t *__restrict__ out_sum,
     int64_t *__restrict__ out_min, int64_t *__restrict__ out_max) {
     __shared__ uint32_t wsc[SEG_B / 64];
@@ -2247,7 +2379,7 @@ __global__ __launch_bounds__(SEG_B) void k_seg_stats(
         uint64_t nk = (c0g + SEG_IPT < n) ? k[PK ? 2 * (c0g + SEG_IPT) : c0g + SEG_IPT] : ~kk[SEG_IPT - 1];
         fast = (nk != kk[SEG_IPT - 1]);
     }
-    int64_t segid = (int64_t)head_base[blockIdx.x] + excl - 1;
+    int64_t segid = (int64_t)head_base[(size_t)blockIdx.x * hstride] + excl - 1;
     StatsAcc a;
     a.reset();
     bool have = false, started_here = false;
@@ -2340,27 +2472,15 @@ __global__ __launch_bounds__(SEG_B) void k_seg_stats(
 hipError_t seg_stats(hipStream_t s, const uint64_t *k, const uint64_t *v, uint64_t n,
                      int64_t *out_k, int64_t *out_count, int64_t *out_sum,
                      int64_t *out_min, int64_t *out_max, uint64_t *h_nout, Ws &ws,
-                     bool packed) {
+                     bool packed, const uint32_t *fin_heads) {
     if (n == 0) { *h_nout = 0; return hipSuccess; }
     if (n >= (1ULL << 32)) return hipErrorNotSupported; /* u32 head scan limit */
     uint32_t nb = nblocks_for(n);
-    uint32_t *hc = (uint32_t *)ws.take(((size_t)nb + 1) * 4);
-    if (!hc) return hipErrorOutOfMemory;
-    {
-        ProfScope ps("head_count", s);
-        if (packed)
-            hipLaunchKernelGGL((k_head_count<true>), dim3(nb), dim3(BLOCK), 0, s, k, n, hc);
-        else
-            hipLaunchKernelGGL((k_head_count<false>), dim3(nb), dim3(BLOCK), 0, s, k, n, hc);
-        HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipMemsetAsync(hc + nb, 0, 4, s));
-    {
-        Ws w2 = ws;
-        HIP_TRY(scan_u32_excl(s, hc, (uint64_t)nb + 1, w2));
-    }
+    const uint32_t *hc, *total_d;
+    uint32_t hstride;
+    HIP_TRY(seg_head_bases(s, k, n, packed, fin_heads, ws, &hc, &hstride, &total_d));
     uint32_t total = 0;
-    HIP_TRY(hipMemcpyAsync(&total, hc + nb, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&total, total_d, 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
 
     /* init the four accumulator columns, `total` rows each */
@@ -2376,10 +2496,10 @@ hipError_t seg_stats(hipStream_t s, const uint64_t *k, const uint64_t *v, uint64
         ProfScope ps("seg_stats", s);
         if (packed)
             hipLaunchKernelGGL((k_seg_stats<true>), dim3(nb), dim3(SEG_B), 0, s, k, v, n, hc,
-                               out_k, out_count, out_sum, out_min, out_max);
+                               hstride, out_k, out_count, out_sum, out_min, out_max);
         else
             hipLaunchKernelGGL((k_seg_stats<false>), dim3(nb), dim3(SEG_B), 0, s, k, v, n, hc,
-                               out_k, out_count, out_sum, out_min, out_max);
+                               hstride, out_k, out_count, out_sum, out_min, out_max);
         HIP_TRY(hipGetLastError());
     }
     *h_nout = total;
@@ -2395,10 +2515,12 @@ hipError_t group_sort_stats(hipStream_t s, const uint64_t *in_k, const uint64_t 
     if (n == 0) { *h_nout = 0; return hipSuccess; }
     const uint64_t *sk, *sv;
     int pk = 0;
-    hipError_t e = group_sort_u64(s, in_k, in_v, n, 0, nullptr, 1, &pk, ws, &sk, &sv);
+    const uint32_t *fh = nullptr;
+    hipError_t e = group_sort_u64(s, in_k, in_v, n, 0, nullptr, 1, &pk, ws, &sk, &sv, 0,
+                                  nullptr, &fh);
     if (e != hipSuccess) return e;
     return seg_stats(s, sk, sv, n, out_k, out_count, out_sum, out_min, out_max, h_nout, ws,
-                     pk != 0);
+                     pk != 0, fh);
 }
 
 /* ------------------------------------------------------------------ */
@@ -3061,7 +3183,8 @@ size_t ws_bytes_for(uint64_t n) {
     b += ((size_t)257 * 4 + 255) & ~255ULL;       /* partition starts */
     b += ((size_t)((nb + 15) / 16 + nb / 256 + 2) * 2048 + 255) & ~255ULL; /* group+super descriptors */
     b += (size_t)CLEANUP_WL_CAP * 8 + 512;        /* cleanup long-run worklist */
-    b += ((size_t)nb * 512 * 12 + 255) & ~255ULL; /* f64 lead partials (seg, OP 2) */
+    b += (((size_t)2 * nb + 1) * 4 + 255) & ~255ULL; /* head counts per finish tile */
+    b += ((size_t)nb * 512 * 12 + 511) & ~255ULL; /* chunk leads (seg, every op) */
     b += 1 << 20;                                 /* slack */
     return b;
 }
