@@ -16,6 +16,9 @@ python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.
   --master-port 29513 bench.py --full --force-dist --steps 5 --warmup 2 --no-cpu-baseline
 # scatter phase breakdown (s_memtime instrumentation):
 VEGA_PHASE_PROF=1 python tools/phase_prof.py --rows 200000000
+# bucket finish phase breakdown, and the route sweep its gate rests on:
+VEGA_PHASE_PROF=1 python tools/finish_phase_prof.py --rows 1000000000
+python tools/route_sweep.py
 # profiling (PMC in separate runs; never combined with trace domains):
 export TMPDIR=/tmp
 (cd /tmp && rocprofv3 --kernel-trace --stats -d $OLDPWD/gpurun_out/kt -o kt -- python $OLDPWD/bench.py --rows 200000000 --steps 2 --warmup 1 --no-cpu-baseline)

@@ -1769,6 +1769,18 @@ int vega_phase_prof_read(unsigned long long out[8], int reset) {
     return VEGA_OK;
 }
 
+/* the same for k_bucket_finish (slots 8.. of the buffer): 0 wait for rows +
+ * stage + hash, 1 bucket ordinals, 2 count, 3 scan, 4 store gather + stores +
+ * head count, 5 tail barrier + count store, 6 place, 7 run fix
+ * (tools/finish_phase_prof.py) */
+int vega_fin_phase_prof_read(unsigned long long out[8], int reset) {
+    unsigned long long *b = vega::phase_prof_buf();
+    if (!b) return VEGA_ERR_UNSUPPORTED;
+    if (hipMemcpy(out, b + 8, 8 * 8, hipMemcpyDeviceToHost) != hipSuccess) return VEGA_ERR_HIP;
+    if (reset) (void)hipMemset(b + 8, 0, 8 * 8);
+    return VEGA_OK;
+}
+
 int vega_dev_checksum_pairs(void *stream, const int64_t *keys, const int64_t *vals,
                             uint64_t n, uint64_t *h_sum, void *d_ws, size_t ws_bytes) {
     Ws ws(d_ws, ws_bytes);

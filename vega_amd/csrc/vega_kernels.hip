@@ -872,6 +872,8 @@ __global__ __launch_bounds__(512) void k_scatter_osw(
 
 /* diagnostic per-phase cycle sums (VEGA_PHASE_PROF=1): lazily allocated,
  * read/reset via vega_phase_prof_read() */
+/* slots 0..7 the onesweep scatter's, 8..15 k_bucket_finish's */
+constexpr int PHASE_SLOTS = 16;
 static unsigned long long *g_phase_buf = nullptr;
 static int g_phase_mode = 0; /* 1 = phases only, 2 = + walk counters */
 unsigned long long *phase_prof_buf() {
@@ -881,8 +883,8 @@ unsigned long long *phase_prof_buf() {
         const char *e = getenv("VEGA_PHASE_PROF");
         if (e && (e[0] == '1' || e[0] == '2')) {
             g_phase_mode = e[0] - '0';
-            (void)hipMalloc(&g_phase_buf, 8 * 8);
-            (void)hipMemset(g_phase_buf, 0, 8 * 8);
+            (void)hipMalloc(&g_phase_buf, PHASE_SLOTS * 8);
+            (void)hipMemset(g_phase_buf, 0, PHASE_SLOTS * 8);
         }
     }
     return g_phase_buf;
@@ -1288,7 +1290,10 @@ __global__ void k_group_cleanup_long(const uint64_t *k, const uint32_t *h32,
  * permute rows inside a bucket. Per FIN_FT-row tile a workgroup stages the
  * tile plus FIN_SLACK rows either side in LDS, re-hashes the keys, orders
  * every bucket that intersects the tile by (h32, input position) — the
- * stable sort by hash byte 0, as one wave-private counting sort per bucket —
+ * stable sort by hash byte 0, as a counting sort of all those buckets at once
+ * in block-wide steps (a row's bucket is its ordinal in the span, from one
+ * scan of the bucket-head flags; 16-bit counters per (bucket, byte 0),
+ * FIN_GROUP buckets per turn) —
  * applies k_group_cleanup's relaxed rule to each equal-h32 run, and stores
  * the rows whose final position lies in its own tile. Buckets across a tile
  * edge are computed for both tiles, identically; each row is stored once.
@@ -1307,24 +1312,29 @@ constexpr int FIN_FT = 2048, FIN_SLACK = 256, FIN_BUCKET_CAP = 256, FIN_B = 512;
 constexpr int FIN_SPAN = FIN_FT + 2 * FIN_SLACK;
 constexpr int FIN_LPT = FIN_SPAN / FIN_B; /* staged rows per thread */
 constexpr int FIN_GRID = 512;             /* 2 blocks per CU */
+constexpr int FIN_CHUNKS = FIN_SPAN / 64;  /* (round, wave) runs of 64 staged rows */
+/* buckets counted together: what LDS holds with two blocks per CU (80,688 B
+ * of the 81,920); a tile that meets more takes them in groups of this many */
+constexpr int FIN_GROUP = 56;
+constexpr int FIN_CSTRIDE = 260; /* u16 per bucket: 256 digits, the total, pad to 8 B */
 /* the automatic route takes the finish only from this many (estimated) rows
  * per bucket: the kernel's time grows with the buckets per tile. Measured on
  * uniform keys, finish route against four passes + cleanup: +0.5 ms at 15
  * rows per bucket (2.5e8 rows), -0.1 ms at 21 (3.5e8), -0.5 ms at 24 (4.1e8),
  * -1.3 ms at 33 (5.5e8), -3.4 ms at 60 (1e9); three calls each, spread
- * <= 0.15 ms (profiles/bucket_finish_route_sweep.json) */
+ * <= 0.15 ms (profiles/bucket_finish_route_sweep.json). With the block-wide
+ * ordering the break-even lies near 15 rows per bucket
+ * (profiles/finish_blockwide_route_sweep.json); the gate has not followed yet */
 constexpr double FIN_MIN_BUCKET_ROWS = 24.0;
+/* k_bucket_finish's slots in phase_prof_buf(), after the scatter's 8:
+ * 0 wait for rows + stage + hash, 1 bucket ordinals, 2 count, 3 scan, 4 store
+ * gather + stores + head count, 5 tail barrier + count store, 6 place, 7 run
+ * fix */
+constexpr int FIN_PHASE0 = 8, FIN_PHASES = 8;
 static_assert(FIN_SPAN % FIN_B == 0 && FIN_FT % FIN_B == 0, "whole rounds per block");
 static_assert(FIN_SPAN <= 65536, "span positions are kept as u16");
 static_assert(FIN_SLACK >= FIN_BUCKET_CAP, "a capped bucket must close inside the slack");
 static_assert(FIN_BUCKET_CAP % 64 == 0, "a bucket is ranked in whole wave rounds");
-
-/* orders one wave's LDS accesses across lanes: the hardware runs a wave's
- * LDS instructions in program order, this keeps the compiler to it */
-__device__ __forceinline__ void fin_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
 
 /* inclusive wave64 prefix sum in registers (DPP: shifts inside each row of
  * 16 lanes, then lane 15 of rows 0/2 into rows 1/3 and lane 31 into the
@@ -1377,19 +1387,39 @@ __device__ __forceinline__ void fin_fix_run(const ulonglong2 *s_row, uint16_t *s
     }
 }
 
+/* PROF: per-phase shader-cycle sums into phc[FIN_PHASE0 ..] (diagnostic, see
+ * phase_prof_buf); the plain instance carries no trace of it */
+template <bool PROF>
 __global__ __launch_bounds__(FIN_B) void k_bucket_finish(const uint64_t *in, uint64_t *out,
                                                          uint64_t n, int *err,
-                                                         uint32_t *fin_heads) {
+                                                         uint32_t *fin_heads,
+                                                         unsigned long long *phc) {
     __shared__ ulonglong2 s_row[FIN_SPAN]; /* staged rows, input order */
-    __shared__ uint32_t s_h[FIN_SPAN];     /* h32 per staged row */
     __shared__ uint16_t s_src[FIN_SPAN];   /* final position -> staged row */
-    __shared__ uint16_t s_bk[FIN_SPAN];    /* first row of each bucket in the span */
-    __shared__ __attribute__((aligned(16))) uint32_t s_cnt[FIN_B / 64][256]; /* per wave */
-    __shared__ int s_lo, s_hi, s_bad, s_nbk;
+    /* first row of the span's o-th bucket; [number of buckets] = m */
+    __shared__ uint16_t s_bstart[FIN_SPAN + 2];
+    /* 16-bit counters, two to a word: [bucket of the group][hash byte 0],
+     * after the scan the digit's offset in its bucket, [256] = its rows */
+    __shared__ __attribute__((aligned(16))) uint32_t s_cnt[FIN_GROUP * FIN_CSTRIDE / 2];
+    __shared__ uint32_t s_edge[FIN_CHUNKS]; /* bucket of each 64-row chunk's last row */
+    __shared__ uint32_t s_tot[FIN_CHUNKS];  /* bucket heads in each chunk */
+    __shared__ int s_of, s_ol, s_bad;       /* first/last bucket meeting the tile */
     __shared__ uint32_t s_heads[FIN_B / 64]; /* run heads each wave stored this tile */
+    uint16_t *const s_cnt16 = (uint16_t *)s_cnt;
 
     const uint32_t ntiles = (uint32_t)((n + FIN_FT - 1) / FIN_FT);
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    /* summed in (scalar) registers and added to phc once, when the block is
+     * done: an atomic per mark, ~2e7 a call on six addresses, queues behind
+     * the others, the barriers wait for it, and every phase reads alike */
+    unsigned long long tprev = PROF ? __builtin_amdgcn_s_memtime() : 0;
+    unsigned long long pacc[FIN_PHASES] = {};
+#define VEGA_PHASE_MARK(i)                                                     \
+    if (PROF) {                                                                \
+        unsigned long long tnow = __builtin_amdgcn_s_memtime();                \
+        pacc[i] += tnow - tprev;                                               \
+        tprev = tnow;                                                          \
+    }
 
     /* staged rows [g0, g0 + m) of a tile */
     auto bounds = [&](uint32_t tile, uint64_t *g0, int *m) {
@@ -1399,7 +1429,9 @@ __global__ __launch_bounds__(FIN_B) void k_bucket_finish(const uint64_t *in, uin
         *m = (int)(((n - t1 < FIN_SLACK) ? n : t1 + FIN_SLACK) - *g0);
     };
     ulonglong2 r[FIN_LPT];
-    auto fetch = [&](uint32_t tile) {
+    uint32_t h[FIN_LPT]; /* h32 of the staged rows */
+    int lo_out = 0;      /* first staged row of the buckets meeting the tile */
+    auto fetch =[&](uint32_t tile) {
         uint64_t g0;
         int m;
         bounds(tile, &g0, &m);
@@ -1415,87 +1447,176 @@ __global__ __launch_bounds__(FIN_B) void k_bucket_finish(const uint64_t *in, uin
     /* fills s_src for the whole buckets meeting the tile [a0, a1) (span-local).
      * False, for the whole block, when the tile cannot be finished here. */
     auto order_tile = [&](uint64_t g0, int m, int a0, int a1) -> bool {
-        /* rows are bucket-ascending: the last foreign row left of the tile
-         * and the first one right of it bound the span */
-        const uint32_t bfirst = s_h[a0] >> 8, blast = s_h[a1 - 1] >> 8;
-        for (int li = threadIdx.x; li < a0; li += FIN_B)
-            if ((s_h[li] >> 8) != bfirst && (s_h[li + 1] >> 8) == bfirst) s_lo = li + 1;
-        for (int li = a1 + threadIdx.x; li < m; li += FIN_B)
-            if ((s_h[li] >> 8) != blast && (s_h[li - 1] >> 8) == blast) s_hi = li;
+        /* bucket ordinals: rows are bucket-ascending, so a row's bucket is
+         * the number of bucket heads up to it. Staged row q * FIN_B + tid is
+         * lane `lane` of chunk q * 8 + w, and the chunks are in row order:
+         * ballot + popcount inside the chunk, then every wave scans the
+         * FIN_CHUNKS totals for itself. */
+        uint32_t inc[FIN_LPT], ishead = 0;
+#pragma unroll
+        for (int q = 0; q < FIN_LPT; ++q) {
+            const int li = q * FIN_B + threadIdx.x, c = q * (FIN_B / 64) + w;
+            const uint32_t bk = h[q] >> 8;
+            uint32_t pb = (uint32_t)__shfl_up((int)bk, 1);
+            if (lane == 0) pb = c ? s_edge[c - 1] : ~0u;
+            const bool head = li < m && (li == 0 || bk != pb);
+            ishead |= (uint32_t)head << q;
+            const uint64_t heads = __ballot(head);
+            inc[q] = (uint32_t)__popcll(heads & (~0ull >> (63 - lane)));
+            if (lane == 0) s_tot[c] = (uint32_t)__popcll(heads);
+        }
+        /* the first group's counters (later groups clear them as they go) */
+        for (int i = threadIdx.x; i < FIN_GROUP * FIN_CSTRIDE / 8; i += FIN_B)
+            ((uint4 *)s_cnt)[i] = make_uint4(0, 0, 0, 0);
         __syncthreads();
-        const int lo = s_lo, hi = s_hi;
+        const uint32_t tot = lane < FIN_CHUNKS ? s_tot[lane] : 0;
+        const uint32_t tinc = fin_wave_scan_incl(tot);
+        int ord[FIN_LPT]; /* the row's bucket, as an ordinal in the span */
+#pragma unroll
+        for (int q = 0; q < FIN_LPT; ++q) {
+            const int li = q * FIN_B + threadIdx.x, c = q * (FIN_B / 64) + w;
+            ord[q] = (int)(__shfl((int)(tinc - tot), c) + inc[q]) - 1;
+            if (ishead >> q & 1) s_bstart[ord[q]] = (uint16_t)li;
+            if (li == a0) s_of = ord[q];
+            if (li == a1 - 1) s_ol = ord[q];
+        }
+        const int nb = __shfl((int)tinc, FIN_CHUNKS - 1);
+        if (threadIdx.x == 0) s_bstart[nb] = (uint16_t)m;
+        __syncthreads();
+        VEGA_PHASE_MARK(1)
+        /* the buckets meeting the tile, and the staged rows [lo, hi) they hold */
+        const int of = s_of, nbk = s_ol - of + 1;
+        const int lo = s_bstart[of], hi = s_bstart[of + nbk];
+        lo_out = lo;
         /* not closed: the bucket may continue in rows that are not staged */
         if ((lo == 0 && g0 > 0) || (hi == m && g0 + m < n)) {
             if (threadIdx.x == 0) *err = 1;
             return false;
         }
-        /* bucket heads, in any order */
-        for (int li = lo + threadIdx.x; li < hi; li += FIN_B)
-            if (li == lo || (s_h[li] >> 8) != (s_h[li - 1] >> 8))
-                s_bk[atomicAdd(&s_nbk, 1)] = (uint16_t)li;
-        __syncthreads();
 
-        /* one wave per bucket: counting sort by hash byte 0 on the wave's own
-         * 256 counters — count (the fetched old count is the row's slot among
-         * its equals), exclusive scan, place; then the lane that owns a digit
-         * puts that digit's run right. The wave's LDS operations execute in
-         * program order, so the steps need no block barrier. */
-        /* (the loop is a chain of dependent LDS round trips: the next bucket's
-         * start is read one iteration ahead, and the reads that depend only on
-         * the start go out together) */
-        uint32_t *cnt = s_cnt[w];
-        const int nbk = s_nbk;
-        int bs_next = (w < nbk) ? s_bk[w] : 0;
-        for (int e = w; e < nbk; e += FIN_B / 64) {
-            const int bs = bs_next;
-            bs_next = (e + FIN_B / 64 < nbk) ? s_bk[e + FIN_B / 64] : 0;
-            ((uint4 *)cnt)[lane] = make_uint4(0, 0, 0, 0);
-            const int over = bs + FIN_BUCKET_CAP < hi ? bs + FIN_BUCKET_CAP : bs;
-            const int l0 = bs + lane < hi ? bs + lane : bs;
-            const uint32_t b = s_h[bs] >> 8, bover = s_h[over] >> 8, h0 = s_h[l0];
-            fin_wave_sync();
-            if (over != bs && bover == b) {
-                if (lane == 0) s_bad = 1; /* more than FIN_BUCKET_CAP rows */
-                continue;
-            }
-            uint32_t hh[FIN_BUCKET_CAP / 64], old[FIN_BUCKET_CAP / 64];
-            bool val[FIN_BUCKET_CAP / 64];
-            bool go = true;
+        /* a row of [lo, hi): its bucket's first row, and its bucket among those
+         * meeting the tile */
+        int bs[FIN_LPT], rel[FIN_LPT];
+        bool act[FIN_LPT];
 #pragma unroll
-            for (int q = 0; q < FIN_BUCKET_CAP / 64; ++q) {
-                val[q] = false;
-                if (go) {
-                    const int li = bs + 64 * q + lane;
-                    hh[q] = q == 0 ? h0 : (li < hi ? s_h[li] : 0);
-                    val[q] = li < hi && (hh[q] >> 8) == b;
-                    if (val[q]) old[q] = atomicAdd(&cnt[hh[q] & 0xFF], 1u);
-                    go = __all(val[q]);
+        for (int q = 0; q < FIN_LPT; ++q) {
+            const int li = q * FIN_B + threadIdx.x;
+            act[q] = li >= lo && li < hi;
+            rel[q] = ord[q] - of;
+            bs[q] = act[q] ? s_bstart[ord[q]] : 0;
+            if (act[q] && li - bs[q] >= FIN_BUCKET_CAP) s_bad = 1; /* more than the cap */
+        }
+        /* counting sort by hash byte 0 of all the buckets at once, FIN_GROUP
+         * of them per turn, in block-wide steps: count (the fetched old count
+         * is the row's slot among its equals), scan each bucket's counts (one
+         * wave per bucket, no atomics in that chain), place, put the runs of
+         * equal byte 0 right. */
+        for (int gb = 0; gb < nbk; gb += FIN_GROUP) {
+            if (gb) {
+                for (int i = threadIdx.x; i < FIN_GROUP * FIN_CSTRIDE / 8; i += FIN_B)
+                    ((uint4 *)s_cnt)[i] = make_uint4(0, 0, 0, 0);
+                __syncthreads();
+            }
+            const int ng = nbk - gb < FIN_GROUP ? nbk - gb : FIN_GROUP;
+            bool in[FIN_LPT];
+            int ci[FIN_LPT], old[FIN_LPT];
+#pragma unroll
+            for (int q = 0; q < FIN_LPT; ++q) {
+                in[q] = act[q] && (unsigned)(rel[q] - gb) < (unsigned)FIN_GROUP;
+                ci[q] = in[q] ? (rel[q] - gb) * FIN_CSTRIDE + (int)(h[q] & 0xFF) : 0;
+                const int sh = (ci[q] & 1) * 16;
+                if (in[q]) old[q] = (int)((atomicAdd(&s_cnt[ci[q] >> 1], 1u << sh) >> sh) & 0xFFFF);
+            }
+            __syncthreads();
+            VEGA_PHASE_MARK(2)
+            if (s_bad) { /* oversized bucket */
+                if (threadIdx.x == 0) *err = 1;
+                return false;
+            }
+            /* counts -> each digit's offset in its bucket; a wave takes two
+             * buckets per turn so that their LDS round trips overlap */
+            for (int e = w; e < ng; e += 2 * (FIN_B / 64)) {
+                const bool two = e + FIN_B / 64 < ng;
+                const int ee[2] = {e, two ? e + FIN_B / 64 : e};
+                uint2 c[2];
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+                    c[j] = ((const uint2 *)(s_cnt + ee[j] * (FIN_CSTRIDE / 2)))[lane];
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    const uint32_t c0 = c[j].x & 0xFFFF, c1 = c[j].x >> 16;
+                    const uint32_t c2 = c[j].y & 0xFFFF, c3 = c[j].y >> 16;
+                    const uint32_t sum = c0 + c1 + c2 + c3;
+                    const uint32_t inc = fin_wave_scan_incl(sum), ex = inc - sum;
+                    if (j == 0 || two) {
+                        ((uint2 *)(s_cnt + ee[j] * (FIN_CSTRIDE / 2)))[lane] =
+                            make_uint2(ex | (ex + c0) << 16, (ex + c0 + c1) | (ex + c0 + c1 + c2) << 16);
+                        if (lane == 63) s_cnt16[ee[j] * FIN_CSTRIDE + 256] = (uint16_t)inc;
+                    }
                 }
             }
-            fin_wave_sync();
-            const uint4 c = ((const uint4 *)cnt)[lane];
-            const uint32_t sum = c.x + c.y + c.z + c.w;
-            const uint32_t ex = fin_wave_scan_incl(sum) - sum;
-            ((uint4 *)cnt)[lane] = make_uint4(ex, ex + c.x, ex + c.x + c.y, ex + c.x + c.y + c.z);
-            fin_wave_sync();
+            __syncthreads();
+            VEGA_PHASE_MARK(3)
+            /* a digit's rows are final positions [p0, p0 + cn) */
+            int p0[FIN_LPT], cn[FIN_LPT];
 #pragma unroll
-            for (int q = 0; q < FIN_BUCKET_CAP / 64; ++q)
-                if (val[q])
-                    s_src[bs + (int)(cnt[hh[q] & 0xFF] + old[q])] = (uint16_t)(bs + 64 * q + lane);
-            fin_wave_sync();
-            /* equal byte 0 inside a bucket == equal h32: digit d's rows are a run */
-            if (c.x >= 2) fin_fix_run(s_row, s_src, bs + (int)ex, (int)c.x, err);
-            if (c.y >= 2) fin_fix_run(s_row, s_src, bs + (int)(ex + c.x), (int)c.y, err);
-            if (c.z >= 2) fin_fix_run(s_row, s_src, bs + (int)(ex + c.x + c.y), (int)c.z, err);
-            if (c.w >= 2)
-                fin_fix_run(s_row, s_src, bs + (int)(ex + c.x + c.y + c.z), (int)c.w, err);
-            fin_wave_sync();
+            for (int q = 0; q < FIN_LPT; ++q) {
+                cn[q] = 0;
+                if (in[q]) {
+                    const int off = s_cnt16[ci[q]];
+                    cn[q] = s_cnt16[ci[q] + 1] - off; /* [256] is the bucket's total */
+                    p0[q] = bs[q] + off;
+                    s_src[p0[q] + old[q]] = (uint16_t)(q * FIN_B + threadIdx.x);
+                }
+            }
+            __syncthreads();
+            VEGA_PHASE_MARK(6)
+            /* equal byte 0 inside a bucket == equal h32: the digit's rows are a
+             * run, to be put right as fin_fix_run does. Nearly all runs have
+             * two or three rows: there every row finds its own slot, from the
+             * other rows' staged indices (read here, before anyone rewrites a
+             * slot) and keys. A longer run is put right by the row that
+             * counted first. */
+            uint32_t oth[FIN_LPT]; /* the run's other rows, 16 bits each */
+#pragma unroll
+            for (int q = 0; q < FIN_LPT; ++q) {
+                oth[q] = 0;
+                if (cn[q] == 2) {
+                    oth[q] = s_src[p0[q] + 1 - old[q]];
+                } else if (cn[q] == 3) {
+                    const int s1 = old[q] == 2 ? 0 : old[q] + 1, s2 = old[q] == 0 ? 2 : old[q] - 1;
+                    oth[q] = (uint32_t)s_src[p0[q] + s1] | (uint32_t)s_src[p0[q] + s2] << 16;
+                }
+            }
+            __syncthreads();
+#pragma unroll
+            for (int q = 0; q < FIN_LPT; ++q) {
+                const int li = q * FIN_B + threadIdx.x;
+                const int o1 = (int)(oth[q] & 0xFFFF), o2 = (int)(oth[q] >> 16);
+                if (cn[q] == 2) { /* input order */
+                    const int slot = li > o1;
+                    if (slot != old[q]) s_src[p0[q] + slot] = (uint16_t)li;
+                } else if (cn[q] == 3) {
+                    /* in input order unless the middle row's key differs from
+                     * both others (two breaks): then by key, equal keys in
+                     * input order */
+                    const uint64_t k0 = s_row[li].x, k1 = s_row[o1].x, k2 = s_row[o2].x;
+                    const int rin = (o1 < li) + (o2 < li);
+                    const int r1 = (li < o1) + (o2 < o1);
+                    const bool dirty = rin == 1 ? (k1 != k0 && k2 != k0)
+                                     : r1 == 1 ? (k0 != k1 && k2 != k1)
+                                               : (k0 != k2 && k1 != k2);
+                    const int rkey = (k1 < k0 || (k1 == k0 && o1 < li)) +
+                                     (k2 < k0 || (k2 == k0 && o2 < li));
+                    const int slot = dirty ? rkey : rin;
+                    if (slot != old[q]) s_src[p0[q] + slot] = (uint16_t)li;
+                } else if (cn[q] > 3 && old[q] == 0) {
+                    fin_fix_run(s_row, s_src, p0[q], cn[q], err);
+                }
+            }
         }
         __syncthreads();
-        if (s_bad) { /* oversized bucket: s_src is incomplete */
-            if (threadIdx.x == 0) *err = 1;
-            return false;
-        }
+        VEGA_PHASE_MARK(7)
         return true;
     };
 
@@ -1508,16 +1629,16 @@ __global__ __launch_bounds__(FIN_B) void k_bucket_finish(const uint64_t *in, uin
         int m;
         bounds(tile, &g0, &m);
         const int a0 = (int)(t0 - g0), a1 = (int)(t1 - g0); /* tile, span-local */
-        if (threadIdx.x == 0) { s_lo = 0; s_hi = m; s_bad = 0; s_nbk = 0; }
+        if (threadIdx.x == 0) s_bad = 0;
 #pragma unroll
         for (int q = 0; q < FIN_LPT; ++q) {
             int li = q * FIN_B + threadIdx.x;
-            if (li < m) {
-                s_row[li] = r[q];
-                s_h[li] = (uint32_t)vega_hash_u64(r[q].x);
-            }
+            h[q] = (uint32_t)vega_hash_u64(r[q].x);
+            if (li < m) s_row[li] = r[q];
+            if (lane == 63) s_edge[q * (FIN_B / 64) + w] = h[q] >> 8;
         }
         __syncthreads();
+        VEGA_PHASE_MARK(0)
         const uint32_t next = tile + gridDim.x;
         if (next < ntiles) fetch(next);
         const bool done = order_tile(g0, m, a0, a1);
@@ -1531,7 +1652,7 @@ __global__ __launch_bounds__(FIN_B) void k_bucket_finish(const uint64_t *in, uin
              * branch): two dependent LDS round trips for all the rounds
              * together. Taking it from the lane below, with lane 0 reading
              * LDS, chains five per round: 0.15 ms slower at 1e9 rows. */
-            const int lo = s_lo;
+            const int lo = lo_out;
             uint32_t heads = 0;
             uint16_t si[FIN_FT / FIN_B], sp[FIN_FT / FIN_B];
 #pragma unroll
@@ -1557,6 +1678,7 @@ __global__ __launch_bounds__(FIN_B) void k_bucket_finish(const uint64_t *in, uin
             }
             if (lane == 0) s_heads[w] = heads;
         }
+        VEGA_PHASE_MARK(4)
         __syncthreads(); /* LDS is restaged next */
         if (done && threadIdx.x == 0) {
             uint32_t t = 0;
@@ -1564,8 +1686,12 @@ __global__ __launch_bounds__(FIN_B) void k_bucket_finish(const uint64_t *in, uin
             for (int i = 0; i < FIN_B / 64; ++i) t += s_heads[i];
             fin_heads[tile] = t;
         }
+        VEGA_PHASE_MARK(5)
         tile = next;
     }
+    if (PROF && lane == 0)
+        for (int i = 0; i < FIN_PHASES; ++i) atomicAdd(&phc[FIN_PHASE0 + i], pacc[i]);
+#undef VEGA_PHASE_MARK
 }
 
 /* packed (k,v) rows -> SoA columns (diagnostic entry only) */
@@ -1750,8 +1876,14 @@ hipError_t group_sort_u64(hipStream_t s, const uint64_t *in_k, const uint64_t *i
             ProfScope ps("group_cleanup", s); /* this route's cleanup stage */
             ProfScope pk("bucket_finish", s);
             const uint32_t ntiles = (uint32_t)((n + FIN_FT - 1) / FIN_FT);
-            hipLaunchKernelGGL(k_bucket_finish, dim3(ntiles < FIN_GRID ? ntiles : FIN_GRID),
-                               dim3(FIN_B), 0, s, cur_k, pB, n, d_err, fh_d);
+            unsigned long long *phc = phase_prof_buf();
+            const dim3 grid(ntiles < FIN_GRID ? ntiles : FIN_GRID);
+            if (phc)
+                hipLaunchKernelGGL(k_bucket_finish<true>, grid, dim3(FIN_B), 0, s, cur_k, pB, n,
+                                   d_err, fh_d, phc);
+            else
+                hipLaunchKernelGGL(k_bucket_finish<false>, grid, dim3(FIN_B), 0, s, cur_k, pB, n,
+                                   d_err, fh_d, nullptr);
             HIP_TRY(hipGetLastError());
         }
         int fl[2] = {0, 0};
