@@ -69,6 +69,14 @@ typedef enum {
 } vega_pred_t;
 /* columns of the stats_by_key combiner C = (count, sum, min, max) */
 typedef enum { VEGA_STAT_COUNT = 0, VEGA_STAT_SUM = 1, VEGA_STAT_MIN = 2, VEGA_STAT_MAX = 3 } vega_stat_t;
+/* join flavours (vega_gpu_join_kind); 0-3 give (K,(Option<V>,Option<W>))
+ * rows, 4-5 filter A by key membership in B */
+typedef enum {
+    VEGA_JOIN_INNER = 0, VEGA_JOIN_LEFT_OUTER = 1, VEGA_JOIN_RIGHT_OUTER = 2,
+    VEGA_JOIN_FULL_OUTER = 3, VEGA_JOIN_LEFT_SEMI = 4, VEGA_JOIN_LEFT_ANTI = 5
+} vega_join_kind_t;
+#define VEGA_JOIN_HAS_A 1   /* bit set in present[i]: the row carries an A value */
+#define VEGA_JOIN_HAS_B 2
 
 typedef struct vega_ctx vega_ctx_t;
 typedef uint64_t vega_rdd_t;      /* opaque RDD handle, 0 = invalid */
@@ -120,6 +128,40 @@ int vega_gpu_sort_by_key(vega_ctx_t *ctx, vega_rdd_t rdd, vega_rdd_t *out);
 /* inner join via sorted runs (co_grouped_rdd.rs:206-249 + pair_rdd.rs:104-121) */
 int vega_gpu_join(vega_ctx_t *ctx, vega_rdd_t a, vega_rdd_t b, uint32_t nparts,
                   vega_rdd_t *out);
+/* the rest of the join family. The reference has inner join only; the
+ * semantics are Spark's, defined over the reference's cogroup
+ * (pair_rdd.rs:123-155) as Spark defines them: per key with value lists
+ * (Vs, Ws), LEFT_OUTER yields (v, None) for each v when Ws is empty, else the
+ * cross product; RIGHT_OUTER and FULL_OUTER are the symmetric cases; INNER is
+ * pair_rdd.rs:104-121. Inputs: plain pair rdds, never modified (grouped /
+ * stats / join-result handles or a kind outside the enum: VEGA_ERR_INVALID;
+ * ngpus > 1 context: VEGA_ERR_UNSUPPORTED; a side or an output of 2^32 rows
+ * or more: VEGA_ERR_UNSUPPORTED with the exact u64 total in
+ * vega_gpu_last_error, as vega_gpu_join).
+ * Kinds 0-3 (both sides i64-valued, as vega_gpu_join) return a JOIN-RESULT
+ * rdd: keys, va, vb and one presence byte per row (VEGA_JOIN_HAS_A |
+ * VEGA_JOIN_HAS_B). An absent side's value slot holds 0 and its bit is clear
+ * — 0 is a legal value, only the bit tells. Collect with
+ * vega_gpu_collect_join_outer (or vega_gpu_collect_join: the three columns,
+ * 0 in absent slots); vega_gpu_count is the row count; the device-side
+ * actions reject it like any join result. INNER is vega_gpu_join: the same
+ * rows in the same order, no presence column stored.
+ * ROW ORDER of kinds 0-3: A's rows in the grouped order vega_gpu_join uses
+ * (stable: equal keys keep A's row order), each followed by its matches in
+ * B's grouped order (B's row order within a key) or, under LEFT / FULL, by
+ * one HAS_A row when it has none. FULL then appends every B row no A row
+ * matched, in B's grouped order, as HAS_B rows. RIGHT is the mirror image (B
+ * rows drive, each with its A matches in A's row order or one HAS_B row);
+ * va is always A's value and vb always B's. So the present == 3 rows of LEFT
+ * or FULL, in order, are exactly vega_gpu_join's rows.
+ * LEFT_SEMI / LEFT_ANTI return a PLAIN pair rdd, usable by every op and
+ * action: the rows of A whose key does / does not occur in B (Spark's
+ * subtractByKey is the anti join), in A's ORIGINAL row order with all
+ * duplicates — a filter with a key-membership predicate. B's values are
+ * never looked at; A's values are 8 opaque bytes, so an f64-valued A is
+ * accepted and the result keeps A's value type and nparts. */
+int vega_gpu_join_kind(vega_ctx_t *ctx, vega_rdd_t a, vega_rdd_t b, vega_join_kind_t kind,
+                       uint32_t nparts, vega_rdd_t *out);
 /* distinct (rdd.rs:501-531): the deduplicated KEY SET (the element column of
  * this typed engine is the key). Result values are zeroed — use
  * vega_gpu_group_count for (key, count). */
@@ -188,6 +230,11 @@ int vega_gpu_collect(vega_ctx_t *ctx, vega_rdd_t rdd, int64_t *keys, void *vals,
 /* collect of a join result (K,(V,W)) — pair_rdd.rs:104-121's output shape */
 int vega_gpu_collect_join(vega_ctx_t *ctx, vega_rdd_t rdd, int64_t *keys,
                           int64_t *va, int64_t *vb, uint64_t *n);
+/* collect of any join result with its presence column (present[i] = HAS_A |
+ * HAS_B bits; an inner result stores none and reports 3 for every row).
+ * keys == NULL queries *n; all four arrays sized *n. */
+int vega_gpu_collect_join_outer(vega_ctx_t *ctx, vega_rdd_t rdd, int64_t *keys, int64_t *va,
+                                int64_t *vb, uint8_t *present, uint64_t *n);
 /* collect of a grouped rdd (vega_gpu_group_by_key): keys[nk],
  * offsets[nk+1] (u64), values[nvals] (int64 or double per the source rdd).
  * Query sizes with keys == NULL. */
@@ -393,6 +440,26 @@ int vega_dev_join_grouped(void *stream, const int64_t *ak, const int64_t *av, ui
                           int order_mode,
                           int64_t *out_k, int64_t *out_va, int64_t *out_vb,
                           uint64_t cap, uint64_t *h_nout, void *d_ws, size_t ws_bytes);
+
+/* vega_dev_join_grouped for the kinds 0-3 of vega_join_kind_t — the
+ * rank-local step of an outer join: after the hash exchange both sides of a
+ * rank hold the same keys, so no row's match lives on another rank. Both
+ * sides are already in the order named by order_mode (0/1/2 as above) and are
+ * NOT modified. Rows, row order and the presence bytes are those of
+ * vega_gpu_join_kind; INNER fills out_present with 3. out_* sized cap.
+ * out_k == NULL is a count-only query. *h_nout = the rows the join holds,
+ * also when that exceeds cap — then the call returns VEGA_ERR_CAP and writes
+ * nothing. d_ws must hold vega_dev_ws_bytes(max(na, nb)) bytes, else
+ * VEGA_ERR_CAP. order_mode or kind out of range: VEGA_ERR_INVALID before any
+ * device call; na == 0 && nb == 0: VEGA_OK with *h_nout = 0, likewise without
+ * one. A side or a total of 2^32 rows or more: VEGA_ERR_UNSUPPORTED.
+ * Synchronizes the stream. */
+int vega_dev_join_grouped_kind(void *stream, const int64_t *ak, const int64_t *av, uint64_t na,
+                               const int64_t *bk, const int64_t *bv, uint64_t nb,
+                               int order_mode, int kind,
+                               int64_t *out_k, int64_t *out_va, int64_t *out_vb,
+                               uint8_t *out_present, uint64_t cap, uint64_t *h_nout,
+                               void *d_ws, size_t ws_bytes);
 
 /* order-independent multiset checksum of device rows (same formula as
  * oracle_checksum_pairs_i64) — large-size parity checks without D2H */

@@ -11,6 +11,11 @@ python bench.py --full --op group_count --dist zipf --steps 4 --warmup 1 --no-cp
 python bench.py --full --op sort  --rows 2000000000 --steps 3 --warmup 1 --no-cpu-baseline  # C3 official total size, 1 GPU
 python bench.py --full --op join  --rows 500000000 --steps 3 --warmup 1 --no-cpu-baseline   # C4 shape
 python bench.py --full --dtype f64 --steps 5 --warmup 2 --no-cpu-baseline                   # C1 f64 variant (deterministic)
+# the join kinds next to vega_gpu_join on the C4 shape (--inner-only measures a
+# checkout that predates join_kind with the same tool):
+python tools/bench_join_kinds.py --rows 100000000 --out profiles/join_kinds_1e8.json
+python tools/bench_join_kinds.py --rows 500000000 --out profiles/join_kinds_1e9.json
+python tools/bench_join_kinds.py --rows 500000000 --kinds RIGHT_OUTER,LEFT_OUTER,FULL_OUTER --out profiles/join_kinds_1e9_outer_only.json
 # RCCL exchange path on hardware (1 GPU, world 1):
 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 \
   --master-port 29513 bench.py --full --force-dist --steps 5 --warmup 2 --no-cpu-baseline

@@ -42,6 +42,9 @@ struct RddImpl {
     bool stats = false;
     void *d_min = nullptr;
     void *d_max = nullptr;
+    /* outer join result (vega_gpu_join_kind 1-3): d_k / d_v / d_v2 as a join
+     * result, plus one presence byte per row (HAS_A | HAS_B) */
+    uint8_t *d_present = nullptr;
     /* multi-GPU (ngpus > 1): per-device shards; d_k/d_v above are device 0's
      * shard so the single-GPU code paths stay untouched for G == 1 */
     std::vector<int64_t *> mk;
@@ -163,6 +166,7 @@ static void free_rdd_buffers(vega_ctx *c, RddImpl *r) {
     if (r->d_v2) (void)hipFree(r->d_v2);
     if (r->d_min) (void)hipFree(r->d_min);
     if (r->d_max) (void)hipFree(r->d_max);
+    if (r->d_present) (void)hipFree(r->d_present);
 }
 
 int vega_gpu_shutdown(vega_ctx_t *c) {
@@ -643,6 +647,163 @@ int vega_gpu_collect_join(vega_ctx_t *c, vega_rdd_t rdd, int64_t *keys,
         CTX_TRY(c, hipMemcpyAsync(keys, r->d_k, r->n * 8, hipMemcpyDeviceToHost, c->stream));
         CTX_TRY(c, hipMemcpyAsync(va, r->d_v, r->n * 8, hipMemcpyDeviceToHost, c->stream));
         CTX_TRY(c, hipMemcpyAsync(vb, r->d_v2, r->n * 8, hipMemcpyDeviceToHost, c->stream));
+    }
+    CTX_TRY(c, hipStreamSynchronize(c->stream));
+    return VEGA_OK;
+}
+
+static_assert(JOIN_KIND_INNER == VEGA_JOIN_INNER && JOIN_KIND_LEFT_OUTER == VEGA_JOIN_LEFT_OUTER &&
+              JOIN_KIND_RIGHT_OUTER == VEGA_JOIN_RIGHT_OUTER &&
+              JOIN_KIND_FULL_OUTER == VEGA_JOIN_FULL_OUTER && JOIN_HAS_A == VEGA_JOIN_HAS_A &&
+              JOIN_HAS_B == VEGA_JOIN_HAS_B, "kernel TU and header agree on the join kinds");
+
+/* LEFT_SEMI / LEFT_ANTI: B's distinct keys in grouping order, then a
+ * membership lookup per row of A in A's own order and a stable compaction —
+ * filter with a key-membership predicate. A is not grouped at all. */
+static int join_member(vega_ctx *c, RddImpl *ra, RddImpl *rb, int want, vega_rdd_t *out) {
+    int rc = ensure_ws(c, ra->n > rb->n ? ra->n : rb->n);
+    if (rc) return rc;
+    vega_rdd_t hb = 0;
+    RddImpl *sb = nullptr, *o = nullptr;
+    rc = new_rdd(c, rb->n ? rb->n : 1, 0, 1, &sb, &hb);
+    if (rc) return rc;
+    sb->n = rb->n;
+    int64_t *kb_u = nullptr, *cntb = nullptr;
+    uint64_t nkb = 0, nsel = 0;
+    int mode = 2;
+    hipError_t e = hipSuccess;
+    int ret = VEGA_ERR_HIP;
+    do {
+        if (rb->n) {
+            /* the value column only rides along through the grouping sort */
+            if ((e = hipMemcpyAsync(sb->d_k, rb->d_k, rb->n * 8, hipMemcpyDeviceToDevice, c->stream)) != hipSuccess) break;
+            if ((e = hipMemsetAsync(sb->d_v, 0, rb->n * 8, c->stream)) != hipSuccess) break;
+            int tag = 0;
+            {
+                Ws ws(c->ws, c->ws_bytes);
+                if ((e = group_pairs_inplace(c->stream, sb->d_k, (int64_t *)sb->d_v, sb->n, &tag, ws)) != hipSuccess) break;
+            }
+            mode = tag == 4 ? 2 : 1;
+            if ((e = hipMalloc(&kb_u, rb->n * 8)) != hipSuccess) break;
+            if ((e = hipMalloc(&cntb, rb->n * 8)) != hipSuccess) break;
+            Ws ws(c->ws, c->ws_bytes);
+            if ((e = seg_reduce(c->stream, (const uint64_t *)sb->d_k, (const uint64_t *)sb->d_v,
+                                sb->n, VEGA_OP_COUNT, (uint64_t *)kb_u, cntb, &nkb, ws)) != hipSuccess) break;
+        }
+        int rc2 = new_rdd(c, ra->n ? ra->n : 1, ra->vtype, ra->nparts, &o, out);
+        if (rc2) { ret = rc2; break; }
+        {
+            Ws ws(c->ws, c->ws_bytes);
+            if ((e = member_filter_rows(c->stream, ra->d_k, (const int64_t *)ra->d_v, ra->n, kb_u,
+                                        nkb, mode, want, o->d_k, (int64_t *)o->d_v, &nsel, ws)) != hipSuccess) break;
+        }
+        o->n = nsel;
+        ret = VEGA_OK;
+    } while (0);
+    if (e != hipSuccess) {
+        snprintf(c->err, sizeof c->err, "join_kind: %s", hipGetErrorString(e));
+        if (e == hipErrorNotSupported) ret = VEGA_ERR_UNSUPPORTED;
+    }
+    (void)hipStreamSynchronize(c->stream);
+    if (kb_u) (void)hipFree(kb_u);
+    if (cntb) (void)hipFree(cntb);
+    vega_gpu_free_rdd(c, hb);
+    if (ret != VEGA_OK && *out) { /* no half-built handle is handed out */
+        vega_gpu_free_rdd(c, *out);
+        *out = 0;
+    }
+    return ret;
+}
+
+int vega_gpu_join_kind(vega_ctx_t *c, vega_rdd_t a, vega_rdd_t b, vega_join_kind_t kind,
+                       uint32_t nparts, vega_rdd_t *out) {
+    if (!c || !out) return VEGA_ERR_INVALID;
+    *out = 0;
+    if ((int)kind < VEGA_JOIN_INNER || (int)kind > VEGA_JOIN_LEFT_ANTI) return VEGA_ERR_INVALID;
+    if (c->ngpus > 1) return VEGA_ERR_UNSUPPORTED;
+    RddImpl *ra = get_rdd(c, a), *rb = get_rdd(c, b);
+    if (!ra || !rb) return VEGA_ERR_INVALID;
+    if (ra->grouped || ra->stats || ra->d_v2 || rb->grouped || rb->stats || rb->d_v2)
+        return VEGA_ERR_INVALID;
+    if (ra->n >= (1ULL << 32) || rb->n >= (1ULL << 32)) {
+        snprintf(c->err, sizeof c->err, "join_kind: a side of %llu rows exceeds the 2^32-1 per-call limit",
+                 (unsigned long long)(ra->n > rb->n ? ra->n : rb->n));
+        return VEGA_ERR_UNSUPPORTED;
+    }
+    if (kind == VEGA_JOIN_LEFT_SEMI || kind == VEGA_JOIN_LEFT_ANTI)
+        return join_member(c, ra, rb, kind == VEGA_JOIN_LEFT_SEMI ? 1 : 0, out);
+    if (ra->vtype || rb->vtype) return VEGA_ERR_INVALID;
+    if (kind == VEGA_JOIN_INNER) return vega_gpu_join(c, a, b, nparts, out);
+
+    vega_rdd_t ha = 0, hb = 0;
+    RddImpl *sa = nullptr, *sb = nullptr, *o = nullptr;
+    int mode = 2, ret = VEGA_ERR_HIP;
+    uint64_t total = 0, n2 = 0;
+    hipError_t e = hipSuccess;
+    int rc = group_two_sides(c, ra, rb, nparts, &ha, &hb, &sa, &sb, &mode);
+    if (rc) { ret = rc; goto cleanup; }
+    {
+        Ws ws(c->ws, c->ws_bytes);
+        e = join_sorted_kind(c->stream, sa->d_k, (const int64_t *)sa->d_v, sa->n, sb->d_k,
+                             (const int64_t *)sb->d_v, sb->n, mode, (int)kind, nullptr, nullptr,
+                             nullptr, nullptr, 0, &total, ws);
+        if (e != hipSuccess) goto cleanup;
+    }
+    if (total >= (1ULL << 32)) { /* u32 emit scan limit: refuse loudly */
+        snprintf(c->err, sizeof c->err, "join output %llu rows exceeds the 2^32-1 per-call limit",
+                 (unsigned long long)total);
+        ret = VEGA_ERR_UNSUPPORTED;
+        goto cleanup;
+    }
+    rc = new_rdd(c, total ? total : 1, 0, nparts, &o, out);
+    if (rc) { ret = rc; goto cleanup; }
+    if ((e = hipMalloc(&o->d_v2, (total ? total : 1) * 8)) != hipSuccess) goto cleanup;
+    if ((e = hipMalloc((void **)&o->d_present, total ? total : 1)) != hipSuccess) goto cleanup;
+    {
+        Ws ws(c->ws, c->ws_bytes);
+        e = join_sorted_kind(c->stream, sa->d_k, (const int64_t *)sa->d_v, sa->n, sb->d_k,
+                             (const int64_t *)sb->d_v, sb->n, mode, (int)kind, o->d_k,
+                             (int64_t *)o->d_v, (int64_t *)o->d_v2, o->d_present, total, &n2, ws);
+        if (e != hipSuccess) goto cleanup;
+    }
+    if (n2 != total) {
+        snprintf(c->err, sizeof c->err, "join_kind emit: n2=%llu total=%llu",
+                 (unsigned long long)n2, (unsigned long long)total);
+        goto cleanup;
+    }
+    o->n = total;
+    ret = VEGA_OK;
+cleanup:
+    if (e != hipSuccess) {
+        snprintf(c->err, sizeof c->err, "join_kind: %s", hipGetErrorString(e));
+        ret = e == hipErrorNotSupported ? VEGA_ERR_UNSUPPORTED : VEGA_ERR_HIP;
+    }
+    if (ha) vega_gpu_free_rdd(c, ha); /* syncs the stream first */
+    if (hb) vega_gpu_free_rdd(c, hb);
+    if (ret != VEGA_OK && *out) { /* no half-built handle is handed out */
+        vega_gpu_free_rdd(c, *out);
+        *out = 0;
+    }
+    return ret;
+}
+
+int vega_gpu_collect_join_outer(vega_ctx_t *c, vega_rdd_t rdd, int64_t *keys, int64_t *va,
+                                int64_t *vb, uint8_t *present, uint64_t *n) {
+    if (!c || !n) return VEGA_ERR_INVALID;
+    RddImpl *r = get_rdd(c, rdd);
+    if (!r || r->grouped || r->stats || !r->d_v2) return VEGA_ERR_INVALID;
+    if (!keys) { *n = r->n; return VEGA_OK; }
+    if (*n < r->n) return VEGA_ERR_CAP;
+    if (!va || !vb || !present) return VEGA_ERR_INVALID;
+    *n = r->n;
+    if (r->n) {
+        CTX_TRY(c, hipMemcpyAsync(keys, r->d_k, r->n * 8, hipMemcpyDeviceToHost, c->stream));
+        CTX_TRY(c, hipMemcpyAsync(va, r->d_v, r->n * 8, hipMemcpyDeviceToHost, c->stream));
+        CTX_TRY(c, hipMemcpyAsync(vb, r->d_v2, r->n * 8, hipMemcpyDeviceToHost, c->stream));
+        if (r->d_present)
+            CTX_TRY(c, hipMemcpyAsync(present, r->d_present, r->n, hipMemcpyDeviceToHost, c->stream));
+        else
+            memset(present, VEGA_JOIN_HAS_A | VEGA_JOIN_HAS_B, r->n);
     }
     CTX_TRY(c, hipStreamSynchronize(c->stream));
     return VEGA_OK;
@@ -1680,6 +1841,32 @@ int vega_dev_join_grouped(void *stream, const int64_t *ak, const int64_t *av, ui
     hipError_t e = join_sorted((hipStream_t)stream, ak, av, na, bk, bv, nb, order_mode,
                                out_k, out_va, out_vb, cap, h_nout, ws);
     return e == hipSuccess ? VEGA_OK : VEGA_ERR_HIP;
+}
+
+/* the kinds 0-3 on sides already in one order (see vega_gpu.h). The argument
+ * guards come before anything touches the device. */
+int vega_dev_join_grouped_kind(void *stream, const int64_t *ak, const int64_t *av, uint64_t na,
+                               const int64_t *bk, const int64_t *bv, uint64_t nb,
+                               int order_mode, int kind,
+                               int64_t *out_k, int64_t *out_va, int64_t *out_vb,
+                               uint8_t *out_present, uint64_t cap, uint64_t *h_nout,
+                               void *d_ws, size_t ws_bytes) {
+    if (!h_nout) return VEGA_ERR_INVALID;
+    *h_nout = 0;
+    if (order_mode < 0 || order_mode > 2) return VEGA_ERR_INVALID;
+    if (kind < VEGA_JOIN_INNER || kind > VEGA_JOIN_FULL_OUTER) return VEGA_ERR_INVALID;
+    if (na == 0 && nb == 0) return VEGA_OK;
+    if (na >= (1ULL << 32) || nb >= (1ULL << 32)) return VEGA_ERR_UNSUPPORTED;
+    if ((na && (!ak || !av)) || (nb && (!bk || !bv))) return VEGA_ERR_INVALID;
+    if (out_k && (!out_va || !out_vb || !out_present)) return VEGA_ERR_INVALID;
+    if (!d_ws || ws_bytes < ws_bytes_for(na > nb ? na : nb)) return VEGA_ERR_CAP;
+    Ws ws(d_ws, ws_bytes);
+    hipError_t e = join_sorted_kind((hipStream_t)stream, ak, av, na, bk, bv, nb, order_mode, kind,
+                                    out_k, out_va, out_vb, out_present, cap, h_nout, ws);
+    if (e == hipErrorInvalidValue && *h_nout > cap) return VEGA_ERR_CAP; /* nothing written */
+    if (e == hipSuccess && out_k) e = hipStreamSynchronize((hipStream_t)stream);
+    if (e == hipErrorNotSupported) return VEGA_ERR_UNSUPPORTED;
+    return e == hipSuccess ? VEGA_OK : (e == hipErrorOutOfMemory ? VEGA_ERR_NOMEM : VEGA_ERR_HIP);
 }
 
 size_t vega_dev_select_ws_bytes(uint64_t num, uint64_t cand_cap) {

@@ -144,6 +144,34 @@ hipError_t join_sorted(hipStream_t s, const int64_t *ak, const int64_t *av, uint
                        int64_t *out_k, int64_t *out_va, int64_t *out_vb,
                        uint64_t cap, uint64_t *h_nout, Ws &ws);
 
+/* vega_join_kind_t 0-3 and the presence bits, for the kernel TU (vega_api.hip
+ * asserts they equal the header's) */
+enum { JOIN_KIND_INNER = 0, JOIN_KIND_LEFT_OUTER = 1, JOIN_KIND_RIGHT_OUTER = 2,
+       JOIN_KIND_FULL_OUTER = 3 };
+constexpr uint8_t JOIN_HAS_A = 1, JOIN_HAS_B = 2;
+
+/* join_sorted for kinds 0-3, with a presence byte per output row (HAS_A |
+ * HAS_B; an absent side's value slot is stored as 0). Row order: the driving
+ * side's rows in their order (A; B for RIGHT), each followed by its matches
+ * in the other side's order or by one row of its own; FULL then appends the
+ * B rows no A row matched, in B's order. Either side may be empty.
+ * out_k == nullptr: count-only. *h_nout = the u64 row total (after a stream
+ * sync), also when it exceeds cap — then hipErrorInvalidValue and nothing is
+ * written. A side or a total of 2^32 rows or more: hipErrorNotSupported.
+ * INNER runs join_sorted itself and fills the presence column with 3. */
+hipError_t join_sorted_kind(hipStream_t s, const int64_t *ak, const int64_t *av, uint64_t na,
+                            const int64_t *bk, const int64_t *bv, uint64_t nb,
+                            int mode, int kind,
+                            int64_t *out_k, int64_t *out_va, int64_t *out_vb,
+                            uint8_t *out_present, uint64_t cap, uint64_t *h_nout, Ws &ws);
+
+/* semi (want=1) / anti (want=0) join: the rows of A, in A's row order, whose
+ * key is / is not in the distinct list kb_u (sorted under `mode`). Values
+ * are 8 opaque bytes. out_* hold na rows; *h_nout after a stream sync. */
+hipError_t member_filter_rows(hipStream_t s, const int64_t *ak, const int64_t *av, uint64_t na,
+                              const int64_t *kb_u, uint64_t nkb, int mode, int want,
+                              int64_t *out_k, int64_t *out_v, uint64_t *h_nout, Ws &ws);
+
 /* in-place grouping-order sort (the cheap 4-5 pass order joins use) */
 hipError_t group_pairs_inplace(hipStream_t s, int64_t *keys, int64_t *vals,
                                uint64_t n, int *order_tag, Ws &ws);

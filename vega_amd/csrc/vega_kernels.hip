@@ -10,6 +10,8 @@
  *   K5 radix_sort_u64 (signed order) <- sort_by_key (absent in reference)
  *   K4 join_sorted     <- CoGroupedRdd::compute HashMap-of-vecs
  *                         (/root/reference/src/rdd/co_grouped_rdd.rs:206-249)
+ *      join_sorted_kind   the outer kinds over the same machinery (Spark
+ *                         semantics; the reference has inner join only)
  *
  * Design (MI355X): all kernels are HBM-bound integer work — no MFMA. 64-lane
  * wavefront ballot matching ranks digits in-register; tiles are staged and
@@ -3660,6 +3662,279 @@ hipError_t join_sorted(hipStream_t s, const int64_t *ak, const int64_t *av, uint
                            counts, b_lo, out_k, out_va, out_vb, cap);
         HIP_TRY(hipGetLastError());
     }
+    return hipSuccess;
+}
+
+/* ------------------------------------------------------------------ */
+/* outer joins (Spark's leftOuterJoin / rightOuterJoin / fullOuterJoin over
+ * the cogroup of pair_rdd.rs:123-155): the inner join's count pass on the
+ * DRIVING side, an emit that also writes a row for a count of 0, and for
+ * FULL a second windowed pass that finds the rows of the other side no
+ * driving row matched. RIGHT is LEFT with the sides swapped by the caller of
+ * the kernels (pointers and presence bits), not a third kernel body. */
+
+constexpr uint32_t JOIN_NO_MATCH = 0xFFFFFFFFu; /* b_lo of a driving row without a match */
+
+/* a driving row without a match still emits one row: counts[i] 0 -> 1 with
+ * the sentinel in b_lo (a real lower bound is <= n_other < 2^32 - 1 whenever
+ * the count is nonzero). Fused with the u64 total that has to precede the
+ * u32 scan (k_sum_u32_u64's job in the inner join). */
+__global__ void k_outer_fix_sum(uint32_t *counts, uint32_t *b_lo, uint64_t n,
+                                unsigned long long *out) {
+    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    unsigned long long acc = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        uint32_t c = counts[i];
+        if (c == 0) {
+            counts[i] = c = 1;
+            b_lo[i] = JOIN_NO_MATCH;
+        }
+        acc += c;
+    }
+    for (int off = 32; off > 0; off >>= 1)
+        acc += (unsigned long long)__shfl_down((unsigned long long)acc, off);
+    if ((threadIdx.x & 63) == 0 && acc) atomicAdd(out, acc);
+}
+
+/* thread per driving row, as k_join_emit (a hot key's cross product is
+ * written by one thread there too). d* = driving side, o* = the other side;
+ * out_vd / out_vo are the output columns of the two sides in that order, so
+ * RIGHT passes (out_vb, out_va) and drive_bit = HAS_B. An absent slot is
+ * stored as 0, never left as allocated. The presence bytes are plain cached
+ * stores: neighbouring threads own neighbouring output rows, so a wave's
+ * bytes fall into one or two 64-B lines that L2 merges before they leave. */
+__global__ void k_join_emit_outer(const int64_t *dk, const int64_t *dv, uint64_t nd,
+                                  const int64_t *ov, const uint32_t *scan,
+                                  const uint32_t *o_lo, int64_t *out_k,
+                                  int64_t *out_vd, int64_t *out_vo, uint8_t *present,
+                                  uint8_t drive_bit, uint64_t cap) {
+    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nd; i += stride) {
+        uint64_t base = scan[i];
+        uint32_t c = scan[i + 1] - (uint32_t)base;
+        int64_t k = dk[i], vd = dv[i];
+        uint32_t lb = o_lo[i];
+        if (lb == JOIN_NO_MATCH) {
+            if (base < cap) {
+                out_k[base] = k;
+                out_vd[base] = vd;
+                out_vo[base] = 0;
+                present[base] = drive_bit;
+            }
+            continue;
+        }
+        for (uint32_t j = 0; j < c; ++j) {
+            uint64_t o = base + j;
+            if (o >= cap) break;
+            out_k[o] = k;
+            out_vd[o] = vd;
+            out_vo[o] = ov[lb + j];
+            present[o] = JOIN_HAS_A | JOIN_HAS_B;
+        }
+    }
+}
+
+/* FULL's second pass: flags[i] = 1 iff row i of the probing side (pk) has no
+ * equal key on the driving side (dk). Same two block-level searches per
+ * 4096-row span as k_join_count — both sides are sorted under one
+ * comparator, so the window holds in this direction too — then a lower bound
+ * and one equality test per row. nd == 0 leaves the window empty and dk
+ * unread. */
+__global__ void k_join_unmatched(const int64_t *pk, uint64_t np, const int64_t *dk,
+                                 uint64_t nd, int mode, uint32_t *flags) {
+    __shared__ uint64_t s_lo, s_hi;
+    uint64_t nspans = (np + TILE - 1) / TILE;
+    for (uint64_t sp = blockIdx.x; sp < nspans; sp += gridDim.x) {
+        uint64_t p0 = sp * TILE;
+        uint64_t p1 = (np - p0 < TILE) ? np : p0 + TILE;
+        if (threadIdx.x == 0) {
+            int64_t kf = pk[p0];
+            uint64_t lo = 0, hi = nd;
+            while (lo < hi) {
+                uint64_t m = (lo + hi) >> 1;
+                if (join_less(mode, dk[m], kf)) lo = m + 1; else hi = m;
+            }
+            s_lo = lo;
+        } else if (threadIdx.x == 64) {
+            int64_t kl = pk[p1 - 1];
+            uint64_t lo = 0, hi = nd;
+            while (lo < hi) {
+                uint64_t m = (lo + hi) >> 1;
+                if (!join_less(mode, kl, dk[m])) lo = m + 1; else hi = m;
+            }
+            s_hi = lo;
+        }
+        __syncthreads();
+        const uint64_t wlo = s_lo, whi = s_hi;
+        __syncthreads(); /* s_lo/s_hi free for the next span */
+        for (uint64_t i = p0 + threadIdx.x; i < p1; i += blockDim.x) {
+            int64_t k = pk[i];
+            uint64_t lo = wlo, hi = whi;
+            while (lo < hi) {
+                uint64_t m = (lo + hi) >> 1;
+                if (join_less(mode, dk[m], k)) lo = m + 1; else hi = m;
+            }
+            flags[i] = (lo < whi && dk[lo] == k) ? 0u : 1u;
+        }
+    }
+}
+
+/* stable compaction of the unmatched rows behind the driving side's rows
+ * (scan = exclusive scan of the flags over np+1) */
+__global__ void k_join_append_unmatched(const int64_t *pk, const int64_t *pv, uint64_t np,
+                                        const uint32_t *scan, uint64_t base,
+                                        int64_t *out_k, int64_t *out_vd, int64_t *out_vo,
+                                        uint8_t *present, uint8_t other_bit, uint64_t cap) {
+    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < np; i += stride) {
+        uint32_t sc = scan[i];
+        if (scan[i + 1] == sc) continue;
+        uint64_t o = base + sc;
+        if (o >= cap) continue;
+        out_k[o] = pk[i];
+        out_vd[o] = 0;
+        out_vo[o] = pv[i];
+        present[o] = other_bit;
+    }
+}
+
+hipError_t join_sorted_kind(hipStream_t s, const int64_t *ak, const int64_t *av, uint64_t na,
+                            const int64_t *bk, const int64_t *bv, uint64_t nb,
+                            int mode, int kind,
+                            int64_t *out_k, int64_t *out_va, int64_t *out_vb,
+                            uint8_t *out_present, uint64_t cap, uint64_t *h_nout, Ws &ws) {
+    if (kind < JOIN_KIND_INNER || kind > JOIN_KIND_FULL_OUTER) return hipErrorInvalidValue;
+    if (kind == JOIN_KIND_INNER) {
+        HIP_TRY(join_sorted(s, ak, av, na, bk, bv, nb, mode, out_k, out_va, out_vb, cap,
+                            h_nout, ws));
+        if (out_k && *h_nout) HIP_TRY(hipMemsetAsync(out_present, 3, *h_nout, s));
+        return hipSuccess;
+    }
+    *h_nout = 0;
+    if (na == 0 && nb == 0) return hipSuccess;
+    if (na >= (1ULL << 32) || nb >= (1ULL << 32)) return hipErrorNotSupported;
+    /* d* drives (every row of it is emitted), o* is probed */
+    const bool swap = kind == JOIN_KIND_RIGHT_OUTER;
+    const int64_t *dk = swap ? bk : ak, *dv = swap ? bv : av;
+    const int64_t *ok = swap ? ak : bk, *ov = swap ? av : bv;
+    const uint64_t nd = swap ? nb : na, no = swap ? na : nb;
+    int64_t *out_vd = swap ? out_vb : out_va, *out_vo = swap ? out_va : out_vb;
+    const uint8_t dbit = swap ? JOIN_HAS_B : JOIN_HAS_A;
+    const uint8_t obit = swap ? JOIN_HAS_A : JOIN_HAS_B;
+    const bool full = kind == JOIN_KIND_FULL_OUTER && no > 0;
+
+    uint32_t *counts = (uint32_t *)ws.take((nd + 1) * 4);
+    uint32_t *o_lo = (uint32_t *)ws.take((nd ? nd : 1) * 4);
+    uint32_t *flags = full ? (uint32_t *)ws.take((no + 1) * 4) : nullptr;
+    unsigned long long *d_total = (unsigned long long *)ws.take(256);
+    if (!counts || !o_lo || !d_total || (full && !flags)) return hipErrorOutOfMemory;
+    const uint32_t gd_all = nblocks_for(nd), gd = gd_all < 2048 ? gd_all : 2048;
+    const uint32_t go_all = nblocks_for(no), go = go_all < 2048 ? go_all : 2048;
+    unsigned long long drive_total = 0;
+    if (nd) {
+        {
+            ProfScope ps("join_count_outer", s);
+            hipLaunchKernelGGL(k_join_count, dim3(gd), dim3(BLOCK), 0, s, dk, nd, ok, no,
+                               mode, counts, o_lo);
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipMemsetAsync(d_total, 0, 8, s));
+        {
+            ProfScope ps("join_outer_fix", s);
+            hipLaunchKernelGGL(k_outer_fix_sum, dim3(gd), dim3(BLOCK), 0, s, counts, o_lo, nd,
+                               d_total);
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipMemcpyAsync(&drive_total, d_total, 8, hipMemcpyDeviceToHost, s));
+    }
+    uint32_t unmatched = 0;
+    if (full) {
+        {
+            ProfScope ps("join_unmatched", s);
+            hipLaunchKernelGGL(k_join_unmatched, dim3(go), dim3(BLOCK), 0, s, ok, no, dk, nd,
+                               mode, flags);
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipMemsetAsync(flags + no, 0, 4, s));
+        {
+            Ws w2 = ws;
+            HIP_TRY(scan_u32_excl(s, flags, no + 1, w2));
+        }
+        HIP_TRY(hipMemcpyAsync(&unmatched, flags + no, 4, hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    const uint64_t total = drive_total + unmatched;
+    *h_nout = total;
+    if (!out_k) return hipSuccess; /* count-only query */
+    if (total >= (1ULL << 32)) return hipErrorNotSupported;
+    if (total > cap) return hipErrorInvalidValue; /* nothing written */
+    if (nd) {
+        HIP_TRY(hipMemsetAsync(counts + nd, 0, 4, s));
+        {
+            Ws w2 = ws;
+            HIP_TRY(scan_u32_excl(s, counts, nd + 1, w2));
+        }
+        ProfScope ps("join_emit_outer", s);
+        hipLaunchKernelGGL(k_join_emit_outer, dim3(gd), dim3(BLOCK), 0, s, dk, dv, nd, ov,
+                           counts, o_lo, out_k, out_vd, out_vo, out_present, dbit, cap);
+        HIP_TRY(hipGetLastError());
+    }
+    if (full && unmatched) {
+        ProfScope ps("join_append_unmatched", s);
+        hipLaunchKernelGGL(k_join_append_unmatched, dim3(go), dim3(BLOCK), 0, s, ok, ov, no,
+                           flags, (uint64_t)drive_total, out_k, out_vd, out_vo, out_present,
+                           obit, cap);
+        HIP_TRY(hipGetLastError());
+    }
+    return hipSuccess;
+}
+
+/* rows of A whose key is (want=1) / is not (want=0) in the sorted distinct
+ * list kb_u, in A's own row order: semi / anti join. Values are 8 opaque
+ * bytes. out_* hold na rows. */
+__global__ void k_compact_rows(const int64_t *keys, const int64_t *vals, uint64_t n,
+                               const uint32_t *scan, int64_t *out_k, int64_t *out_v) {
+    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        uint32_t sc = scan[i];
+        if (scan[i + 1] > sc) {
+            out_k[sc] = keys[i];
+            out_v[sc] = vals[i];
+        }
+    }
+}
+
+hipError_t member_filter_rows(hipStream_t s, const int64_t *ak, const int64_t *av, uint64_t na,
+                              const int64_t *kb_u, uint64_t nkb, int mode, int want,
+                              int64_t *out_k, int64_t *out_v, uint64_t *h_nout, Ws &ws) {
+    *h_nout = 0;
+    if (na == 0) return hipSuccess;
+    if (na >= (1ULL << 32)) return hipErrorNotSupported;
+    Ws w2 = ws;
+    uint32_t *bidx = (uint32_t *)w2.take(na * 4);
+    uint32_t *flags = (uint32_t *)w2.take((na + 1) * 4);
+    if (!bidx || !flags) return hipErrorOutOfMemory;
+    uint32_t gb = (uint32_t)((na / BLOCK) + 1);
+    if (gb > 2048) gb = 2048;
+    {
+        ProfScope ps("member_lookup", s);
+        hipLaunchKernelGGL(k_lookup, dim3(gb), dim3(BLOCK), 0, s, ak, na, kb_u, nkb, mode, bidx);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_member_flags, dim3(gb), dim3(BLOCK), 0, s, bidx, na, want, flags);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipMemsetAsync(flags + na, 0, 4, s));
+    HIP_TRY(scan_u32_excl(s, flags, na + 1, w2));
+    uint32_t total = 0;
+    HIP_TRY(hipMemcpyAsync(&total, flags + na, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (total) {
+        ProfScope ps("member_compact", s);
+        hipLaunchKernelGGL(k_compact_rows, dim3(gb), dim3(BLOCK), 0, s, ak, av, na, flags,
+                           out_k, out_v);
+        HIP_TRY(hipGetLastError());
+    }
+    *h_nout = total;
     return hipSuccess;
 }
 

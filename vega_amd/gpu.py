@@ -37,6 +37,15 @@ PRED_KEY_MOD_EQ = 0
 PRED_VAL_GT = 1
 PRED_KEY_IN_RANGE = 2
 
+JOIN_INNER = 0
+JOIN_LEFT_OUTER = 1
+JOIN_RIGHT_OUTER = 2
+JOIN_FULL_OUTER = 3
+JOIN_LEFT_SEMI = 4
+JOIN_LEFT_ANTI = 5
+JOIN_HAS_A = 1  # bit in a presence byte: the row carries an A value
+JOIN_HAS_B = 2
+
 _lib = None
 
 
@@ -297,6 +306,57 @@ class Rdd:
                                            _pp(k), _pp(va), _pp(vb), ctypes.byref(n)),
                "collect_join", self.ctx._c)
         return k[:n.value], va[:n.value], vb[:n.value]
+
+    def join_kind(self, other, kind, nparts=256):
+        """the join family (vega_gpu_join_kind). JOIN_INNER .. JOIN_FULL_OUTER
+        give a join result (collect_join_outer / collect_join); JOIN_LEFT_SEMI
+        and JOIN_LEFT_ANTI give a plain Rdd: the rows of self whose key does /
+        does not occur in other, in self's row order, value type kept."""
+        out = ctypes.c_uint64()
+        _check(lib().vega_gpu_join_kind(self.ctx._c, ctypes.c_uint64(self.h),
+                                        ctypes.c_uint64(other.h), ctypes.c_int(kind),
+                                        ctypes.c_uint32(nparts), ctypes.byref(out)),
+               "join_kind", self.ctx._c)
+        if kind in (JOIN_LEFT_SEMI, JOIN_LEFT_ANTI):
+            return Rdd(self.ctx, out.value, self.vdtype)
+        r = Rdd(self.ctx, out.value, np.int64)
+        r.is_join = True
+        return r
+
+    def left_outer_join(self, other, nparts=256):
+        return self.join_kind(other, JOIN_LEFT_OUTER, nparts)
+
+    def right_outer_join(self, other, nparts=256):
+        return self.join_kind(other, JOIN_RIGHT_OUTER, nparts)
+
+    def full_outer_join(self, other, nparts=256):
+        return self.join_kind(other, JOIN_FULL_OUTER, nparts)
+
+    def semi_join(self, other, nparts=256):
+        """rows of self whose key occurs in other (row order, duplicates kept)"""
+        return self.join_kind(other, JOIN_LEFT_SEMI, nparts)
+
+    def subtract_by_key(self, other, nparts=256):
+        """Spark's subtractByKey, the anti join: rows of self whose key does
+        not occur in other (row order, duplicates kept)"""
+        return self.join_kind(other, JOIN_LEFT_ANTI, nparts)
+
+    def collect_join_outer(self):
+        """(k, va, vb, present) of any join result; present[i] has JOIN_HAS_A /
+        JOIN_HAS_B set, an absent side's value is 0 (an inner result: all 3)"""
+        n = ctypes.c_uint64(0)
+        _check(lib().vega_gpu_collect_join_outer(self.ctx._c, ctypes.c_uint64(self.h),
+                                                 None, None, None, None, ctypes.byref(n)),
+               "collect_join_outer size", self.ctx._c)
+        k = np.empty(n.value, dtype=np.int64)
+        va = np.empty(n.value, dtype=np.int64)
+        vb = np.empty(n.value, dtype=np.int64)
+        pr = np.empty(n.value, dtype=np.uint8)
+        _check(lib().vega_gpu_collect_join_outer(self.ctx._c, ctypes.c_uint64(self.h),
+                                                 _pp(k), _pp(va), _pp(vb), _pp(pr),
+                                                 ctypes.byref(n)),
+               "collect_join_outer", self.ctx._c)
+        return k[:n.value], va[:n.value], vb[:n.value], pr[:n.value]
 
     # --- actions (rdd.rs collect/count) ---
     def count(self):
@@ -641,6 +701,41 @@ def dev_join_grouped(ak, av, bk, bv, order_mode, out_k, out_va, out_vb, ws_t):
         ctypes.byref(nout), _t(ws_t), ctypes.c_size_t(ws_t.numel())),
         "dev_join_grouped")
     return nout.value
+
+
+def dev_join_grouped_kind(ak, av, bk, bv, order_mode, kind, out=None, ws_t=None):
+    """kinds JOIN_INNER .. JOIN_FULL_OUTER on device sides that are both in
+    the order named by order_mode. Returns (out_k, out_va, out_vb, present,
+    needed), the tensors trimmed to the result. out = (out_k, out_va, out_vb,
+    present) caller-given tensors: when too small the call raises VegaGpuError
+    with rc == -5 (VEGA_ERR_CAP) and .needed = the rows the join holds, and
+    nothing is written. Without them a count-only call sizes them."""
+    import torch
+    na, nb = ak.numel(), bk.numel()
+    if ws_t is None:
+        ws_t = alloc_ws(max(na, nb), ak.device)
+    nout = ctypes.c_uint64(0)
+
+    def call(o, cap):
+        return lib().vega_dev_join_grouped_kind(
+            _stream(), _t(ak), _t(av), ctypes.c_uint64(na),
+            _t(bk), _t(bv), ctypes.c_uint64(nb), ctypes.c_int(order_mode),
+            ctypes.c_int(kind), *[_t(x) if x is not None else None for x in o],
+            ctypes.c_uint64(cap), ctypes.byref(nout),
+            _t(ws_t), ctypes.c_size_t(ws_t.numel()))
+
+    if out is None:
+        _check(call((None, None, None, None), 0), "dev_join_grouped_kind count")
+        m = max(nout.value, 1)
+        out = tuple(torch.empty(m, dtype=torch.int64, device=ak.device) for _ in range(3)) + (
+            torch.empty(m, dtype=torch.uint8, device=ak.device),)
+    rc = call(out, min(x.numel() for x in out))
+    if rc != 0:
+        err = VegaGpuError(f"dev_join_grouped_kind failed rc={rc} (needed {nout.value} rows)")
+        err.rc = rc
+        err.needed = nout.value
+        raise err
+    return tuple(x[:nout.value] for x in out) + (nout.value,)
 
 
 def dev_join_sorted(ak, av, bk, bv, out_k, out_va, out_vb, ws_t):

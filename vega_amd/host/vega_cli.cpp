@@ -345,6 +345,22 @@ int main(int argc, char **argv) {
             auto j = a.join(b, 4);
             CHECK_EQ(j.count(), (uint64_t)6, "join golden count (6 tuples)");
         }
+        /* outer and anti join, expected rows written out by hand; B carries
+         * the value 0, so only the presence byte tells "matched 0" from absent */
+        {
+            using jrow_t = vega::PairRdd::JoinRow;
+            auto a = sc.make_rdd({{1, 10}, {1, 11}, {2, 20}, {3, 30}}, 2);
+            auto b = sc.make_rdd({{1, 0}, {3, 300}, {3, 301}, {4, 400}}, 2);
+            auto got = a.full_outer_join(b, 4).collect_join_outer();
+            std::sort(got.begin(), got.end());
+            std::vector<jrow_t> exp{{1, 10, 0, 3},   {1, 11, 0, 3}, {2, 20, 0, 1}, {3, 30, 300, 3},
+                                    {3, 30, 301, 3}, {4, 0, 400, 2}};
+            CHECK_EQ(got, exp, "full_outer_join hand-written (k, va, vb, present)");
+            CHECK_EQ(a.subtract_by_key(b).collect(), (pairs_t{{2, 20}}),
+                     "subtract_by_key (anti join) keeps A's unmatched rows");
+            CHECK_EQ(a.semi_join(b).collect(), (pairs_t{{1, 10}, {1, 11}, {3, 30}}),
+                     "semi_join keeps A's matched rows in row order");
+        }
         /* sort_by_key: signed order + stability surrogate (sortedness) */
         {
             const uint64_t n = 100000, seed = 777;

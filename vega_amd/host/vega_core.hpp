@@ -20,6 +20,7 @@
 #include <random>
 #include <stdexcept>
 #include <string>
+#include <tuple>
 #include <utility>
 #include <vector>
 
@@ -124,6 +125,58 @@ class PairRdd {
         vega_rdd_t out = 0;
         check(vega_gpu_join(c_, h_, other.h_, num_splits, &out), "join", c_);
         return PairRdd(c_, out, false);
+    }
+    /* the rest of the join family (Spark semantics over the reference's
+     * cogroup, see vega_gpu.h). Kinds 0-3: a join result, collected with
+     * collect_join_outer; LEFT_SEMI / LEFT_ANTI: a plain rdd, the rows of this
+     * one in row order, value type kept. */
+    PairRdd join_kind(const PairRdd &other, vega_join_kind_t kind,
+                      uint32_t num_splits = 256) const {
+        vega_rdd_t out = 0;
+        check(vega_gpu_join_kind(c_, h_, other.h_, kind, num_splits, &out), "join_kind", c_);
+        bool member = kind == VEGA_JOIN_LEFT_SEMI || kind == VEGA_JOIN_LEFT_ANTI;
+        return PairRdd(c_, out, member ? f64_ : false);
+    }
+    PairRdd left_outer_join(const PairRdd &other, uint32_t num_splits = 256) const {
+        return join_kind(other, VEGA_JOIN_LEFT_OUTER, num_splits);
+    }
+    PairRdd right_outer_join(const PairRdd &other, uint32_t num_splits = 256) const {
+        return join_kind(other, VEGA_JOIN_RIGHT_OUTER, num_splits);
+    }
+    PairRdd full_outer_join(const PairRdd &other, uint32_t num_splits = 256) const {
+        return join_kind(other, VEGA_JOIN_FULL_OUTER, num_splits);
+    }
+    PairRdd semi_join(const PairRdd &other, uint32_t num_splits = 256) const {
+        return join_kind(other, VEGA_JOIN_LEFT_SEMI, num_splits);
+    }
+    /* Spark's subtractByKey: the anti join */
+    PairRdd subtract_by_key(const PairRdd &other, uint32_t num_splits = 256) const {
+        return join_kind(other, VEGA_JOIN_LEFT_ANTI, num_splits);
+    }
+    /* one row of a join result: (Option<V>, Option<W>) as values plus the
+     * VEGA_JOIN_HAS_A / VEGA_JOIN_HAS_B bits; an absent value is 0 */
+    struct JoinRow {
+        int64_t k, va, vb;
+        uint8_t present;
+        bool operator==(const JoinRow &o) const {
+            return k == o.k && va == o.va && vb == o.vb && present == o.present;
+        }
+        bool operator<(const JoinRow &o) const {
+            return std::tie(k, va, vb, present) < std::tie(o.k, o.va, o.vb, o.present);
+        }
+    };
+    std::vector<JoinRow> collect_join_outer() const {
+        uint64_t n = 0;
+        check(vega_gpu_collect_join_outer(c_, h_, nullptr, nullptr, nullptr, nullptr, &n),
+              "collect_join_outer size", c_);
+        std::vector<int64_t> k(n), va(n), vb(n);
+        std::vector<uint8_t> p(n);
+        if (n)
+            check(vega_gpu_collect_join_outer(c_, h_, k.data(), va.data(), vb.data(), p.data(), &n),
+                  "collect_join_outer", c_);
+        std::vector<JoinRow> out(n);
+        for (uint64_t i = 0; i < n; i++) out[i] = {k[i], va[i], vb[i], p[i]};
+        return out;
     }
     /* rdd.rs:199-235 narrow transforms as op-enums (device-resident) */
     PairRdd map(vega_map_op_t op, int64_t p0 = 0) const {
