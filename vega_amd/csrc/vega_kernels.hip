@@ -1987,10 +1987,18 @@ __global__ void k_head_count(const uint64_t *k, uint64_t n, uint32_t *hc) {
 }
 
 /* OP: 0 SUM_I64, 1 COUNT, 2 SUM_F64, 3 MIN_I64, 4 MAX_I64.
- * Register-only (no LDS staging): each thread owns one 16-row chunk; the
- * unrolled sequential loads vectorize and every 64 B line is fully consumed
- * by exactly one lane, so the pattern is bandwidth-clean and occupancy is
- * not LDS-bound. */
+ * Each thread owns one SEG_IPT-row chunk, each wave the SEG_SPAN rows of its
+ * 64 chunks. A wave loads its span STRIPED: every load instruction reads
+ * 1 KiB of consecutive rows, 16 B per lane (chunk-per-lane loads touched 64
+ * lines per instruction and took 16 B of each). Heads are flagged in that
+ * layout, the predecessor key coming from the lane below, and one ballot
+ * per load gives the wave's head masks; a chunk's head count and its
+ * exclusive prefix are population counts of those masks.
+ *   fast wave (full span, every row a head: all of C1): the rows go from the
+ *     striped registers to out_k / out_v[first + row], lane-contiguous;
+ *   any other wave: the striped keys, then the values, pass through a
+ *     wave-private 4 KiB of LDS (four blocks still fit a CU), each thread
+ *     takes its own chunk back and the per-chunk code below runs on it. */
 /* Store discipline, every op: no atomics in this kernel, and no slot of
  * out_k / out_v needs initialising. The chunk that holds a run's head
  * plain-stores the run's key and the value accumulated inside that chunk
@@ -2012,6 +2020,22 @@ __global__ void k_head_count(const uint64_t *k, uint64_t n, uint32_t *hc) {
  * chains than 256x16 (the chunk loads are the latency chain) */
 #define SEG_B 512
 #define SEG_IPT 8
+#define SEG_SPAN (64 * SEG_IPT) /* rows per wave */
+
+/* order a wave's own LDS stores before its own LDS loads (and back): the
+ * staged rows change lanes */
+__device__ __forceinline__ void seg_stage_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__device__ __forceinline__ uint64_t seg_lane63(uint64_t x) {
+    uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)x, 63);
+    uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(x >> 32), 63);
+    return ((uint64_t)hi << 32) | lo;
+}
+
 template <int OP, bool PK>
 __global__ __launch_bounds__(SEG_B) void k_seg_emit(
     const uint64_t *__restrict__ k, const void *__restrict__ vv, uint64_t n,
@@ -2019,72 +2043,176 @@ __global__ __launch_bounds__(SEG_B) void k_seg_emit(
     int64_t *__restrict__ out_k, void *__restrict__ out_vv,
     uint32_t *__restrict__ lead_seg, double *__restrict__ lead_part) {
     __shared__ uint32_t wsc[SEG_B / 64];
+    __shared__ __attribute__((aligned(16))) uint64_t stage[SEG_B / 64][SEG_SPAN];
     constexpr bool NEED_V = (OP != 1);
 
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
     const uint64_t tbase = (uint64_t)blockIdx.x * TILE;
     const uint64_t *v = (const uint64_t *)vv;
-    const uint64_t c0g = tbase + (uint64_t)t * SEG_IPT; /* chunk start, global */
+    const uint64_t wbase = tbase + (uint64_t)w * SEG_SPAN; /* span start, global */
+    const bool full = wbase + SEG_SPAN <= n;
+    const uint64_t chunk_id = (uint64_t)blockIdx.x * SEG_B + t;
 
-    uint64_t kk[SEG_IPT], sv[SEG_IPT];
-    if (c0g + SEG_IPT <= n) { /* interior chunk: unguarded 16-B vector loads */
-        if (PK) {
-            const ulonglong2 *rp = reinterpret_cast<const ulonglong2 *>(k) + c0g;
+    /* Striped registers, row offsets in the span:
+     *   packed: rk/rv[i] = row i * 64 + lane (one 16-B row per lane and load)
+     *   SoA:    rk/rv[2q + e] = row q * 128 + 2 * lane + e (two per lane and load)
+     * hm[i]: ballot of "rk[i] is a head" */
+    auto srow = [&](int i) -> uint32_t {
+        return PK ? (uint32_t)(i * 64 + lane) : (uint32_t)((i >> 1) * 128 + 2 * lane + (i & 1));
+    };
+    uint64_t rk[SEG_IPT], rv[SEG_IPT], hm[SEG_IPT];
+    uint64_t gprev = 0; /* key of row wbase - 1 */
+    uint32_t wheads = 0;
+    if (wbase < n) {
+        if (full) { /* unguarded 16-B vector loads */
+            if (PK) {
+                const ulonglong2 *rp = reinterpret_cast<const ulonglong2 *>(k) + wbase + lane;
 #pragma unroll
-            for (int j = 0; j < SEG_IPT; ++j) {
-                ulonglong2 r2 = rp[j];
-                kk[j] = r2.x;
-                sv[j] = r2.y;
-            }
-        } else {
-            const ulonglong2 *kp = reinterpret_cast<const ulonglong2 *>(k + c0g);
-            const ulonglong2 *vp = reinterpret_cast<const ulonglong2 *>(v + c0g);
+                for (int i = 0; i < SEG_IPT; ++i) {
+                    ulonglong2 r2 = rp[i * 64];
+                    rk[i] = r2.x;
+                    rv[i] = r2.y;
+                }
+            } else {
+                const ulonglong2 *kp = reinterpret_cast<const ulonglong2 *>(k + wbase) + lane;
+                const ulonglong2 *vp = reinterpret_cast<const ulonglong2 *>(v + wbase) + lane;
 #pragma unroll
-            for (int j2 = 0; j2 < SEG_IPT / 2; ++j2) {
-                ulonglong2 t2 = kp[j2];
-                kk[2 * j2] = t2.x;
-                kk[2 * j2 + 1] = t2.y;
-                if (NEED_V) {
-                    ulonglong2 u2 = vp[j2];
-                    sv[2 * j2] = u2.x;
-                    sv[2 * j2 + 1] = u2.y;
+                for (int q = 0; q < SEG_IPT / 2; ++q) {
+                    ulonglong2 t2 = kp[q * 64];
+                    rk[2 * q] = t2.x;
+                    rk[2 * q + 1] = t2.y;
+                    if (NEED_V) {
+                        ulonglong2 u2 = vp[q * 64];
+                        rv[2 * q] = u2.x;
+                        rv[2 * q + 1] = u2.y;
+                    }
                 }
             }
-        }
-    } else {
+        } else {
 #pragma unroll
-        for (int j = 0; j < SEG_IPT; ++j) {
-            uint64_t gi = c0g + j;
-            kk[j] = (gi < n) ? k[PK ? 2 * gi : gi] : ~0ULL;
-            if (NEED_V || PK) sv[j] = (gi < n) ? (PK ? k[2 * gi + 1] : v[gi]) : 0;
+            for (int i = 0; i < SEG_IPT; ++i) {
+                uint64_t gi = wbase + srow(i);
+                rk[i] = (gi < n) ? k[PK ? 2 * gi : gi] : ~0ULL;
+                if (NEED_V || PK) rv[i] = (gi < n) ? (PK ? k[2 * gi + 1] : v[gi]) : 0;
+            }
         }
-    }
-    uint64_t prev = (c0g > 0 && c0g <= n) ? k[PK ? 2 * (c0g - 1) : c0g - 1] : 0;
+        if (wbase > 0) gprev = k[PK ? 2 * (wbase - 1) : wbase - 1]; /* one address per wave */
 
-    /* count heads in the chunk */
-    uint32_t cnt = 0;
+        uint64_t carry = gprev; /* key of the row before the load's lane 0 */
 #pragma unroll
-    for (int j = 0; j < SEG_IPT; ++j) {
-        uint64_t gi = c0g + j;
-        if (gi < n) {
-            uint64_t pk = (j > 0) ? kk[j - 1] : prev;
-            cnt += (gi == 0) || (kk[j] != pk);
+        for (int i = 0; i < SEG_IPT; ++i) {
+            uint64_t pk;
+            if (PK || !(i & 1)) {
+                const uint64_t last = PK ? rk[i] : rk[i + 1]; /* the lane's last key of this load */
+                pk = __shfl_up(last, 1);
+                if (lane == 0) pk = carry;
+                carry = seg_lane63(last);
+            } else {
+                pk = rk[i - 1];
+            }
+            uint64_t gi = wbase + srow(i);
+            hm[i] = __ballot(gi < n && (gi == 0 || rk[i] != pk));
+            wheads += (uint32_t)__popcll(hm[i]);
         }
     }
-    /* block exclusive scan of cnt */
-    uint32_t inc = cnt;
-    for (int off = 1; off < 64; off <<= 1) {
-        uint32_t u = __shfl_up(inc, off);
-        if (lane >= off) inc += u;
-    }
-    if (lane == 63) wsc[w] = inc;
+    if (lane == 0) wsc[w] = wheads;
     __syncthreads();
-    uint32_t excl = inc - cnt;
-    for (int i = 0; i < w; ++i) excl += wsc[i];
+    if (wbase >= n) {
+        lead_seg[chunk_id] = 0xFFFFFFFFu;
+        return;
+    }
+    uint32_t wexcl = 0; /* heads of the block's earlier waves */
+    for (int i = 0; i < w; ++i) wexcl += wsc[i];
+    const int64_t tile_base = (int64_t)head_base[(size_t)blockIdx.x * hstride];
+
+    /* Fast wave: 512 length-1 runs (the last may go on: the next chunk's lead
+     * carries the rest). For OP 2 the stored value is 0.0 + x, what the
+     * per-chunk code's accumulator gives. */
+    if (full && wheads == SEG_SPAN) {
+        int64_t *okp = out_k + tile_base + wexcl;
+        uint64_t *ovp = (uint64_t *)out_vv + tile_base + wexcl;
+        auto outv = [&](int i) -> uint64_t {
+            if (OP == 1) return 1ULL;
+            if (OP == 2) {
+                double acc = 0.0;
+                acc += __longlong_as_double((long long)rv[i]);
+                return (uint64_t)__double_as_longlong(acc);
+            }
+            return rv[i];
+        };
+        if (!PK && ((tile_base + wexcl) & 1) == 0) {
+            ulonglong2 *ok2 = (ulonglong2 *)okp + lane;
+            ulonglong2 *ov2 = (ulonglong2 *)ovp + lane;
+#pragma unroll
+            for (int q = 0; q < SEG_IPT / 2; ++q) {
+                ok2[q * 64] = make_ulonglong2(rk[2 * q], rk[2 * q + 1]);
+                ov2[q * 64] = make_ulonglong2(outv(2 * q), outv(2 * q + 1));
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < SEG_IPT; ++i) {
+                okp[srow(i)] = (int64_t)rk[i];
+                ovp[srow(i)] = outv(i);
+            }
+        }
+        lead_seg[chunk_id] = 0xFFFFFFFFu;
+        return;
+    }
+
+    /* General wave: hand the striped rows over through LDS, first the span's
+     * keys, then its values through the same 4 KiB; each thread takes back the
+     * SEG_IPT consecutive ones of its chunk as 16-B slots of two. The slot
+     * index is XOR-swizzled inside a chunk with the chunk's number, so that
+     * the ds_read_b128 at a lane stride of one chunk (64 B) spread over all 16
+     * slots of a bank row in every 16-lane group; the lane-contiguous writes
+     * stay conflict-free. */
+    uint64_t *st = stage[w];
+    auto swz = [](int s) -> int { return s ^ ((s >> 4) & 3); }; /* s: slot of two */
+    auto hand_over = [&](const uint64_t(&src)[SEG_IPT], uint64_t(&dst)[SEG_IPT]) {
+        if (PK) {
+#pragma unroll
+            for (int i = 0; i < SEG_IPT; ++i)
+                st[2 * swz(i * 32 + (lane >> 1)) + (lane & 1)] = src[i];
+        } else {
+#pragma unroll
+            for (int q = 0; q < SEG_IPT / 2; ++q)
+                *reinterpret_cast<ulonglong2 *>(st + 2 * swz(q * 64 + lane)) =
+                    make_ulonglong2(src[2 * q], src[2 * q + 1]);
+        }
+        seg_stage_sync();
+#pragma unroll
+        for (int j2 = 0; j2 < SEG_IPT / 2; ++j2) {
+            ulonglong2 t2 = *reinterpret_cast<const ulonglong2 *>(st + 2 * swz(lane * (SEG_IPT / 2) + j2));
+            dst[2 * j2] = t2.x;
+            dst[2 * j2 + 1] = t2.y;
+        }
+        seg_stage_sync();
+    };
+    uint64_t kk[SEG_IPT], sv[SEG_IPT];
+    hand_over(rk, kk);
+    if (NEED_V || PK) hand_over(rv, sv);
+    const uint64_t c0g = wbase + (uint64_t)lane * SEG_IPT; /* chunk start, global */
+    uint64_t prev = __shfl_up(kk[SEG_IPT - 1], 1); /* key of row c0g - 1 */
+    if (lane == 0) prev = gprev;
+
+    /* heads in the chunk, and in the wave's chunks before it, from the masks:
+     * a chunk's rows are GW consecutive bits in each mask of one load */
+    constexpr int GW = PK ? SEG_IPT : SEG_IPT / 2;
+    const int grp = lane / (64 / GW), gsh = (lane % (64 / GW)) * GW;
+    uint32_t cnt = 0, excl = wexcl;
+#pragma unroll
+    for (int i = 0; i < SEG_IPT; ++i) {
+        const int g = PK ? i : (i >> 1);
+        if (g < grp) {
+            excl += (uint32_t)__popcll(hm[i]);
+        } else if (g == grp) {
+            cnt += (uint32_t)__popcll((hm[i] >> gsh) & ((1ULL << GW) - 1));
+            excl += (uint32_t)__popcll(hm[i] & ((1ULL << gsh) - 1));
+        }
+    }
 
     if (OP == 2) { /* deterministic f64 path (see kernel comment) */
-        uint64_t chunk_id = (uint64_t)blockIdx.x * SEG_B + t;
-        int64_t sid = (int64_t)head_base[(size_t)blockIdx.x * hstride] + excl - 1; /* run open at chunk start */
+        int64_t sid = tile_base + excl - 1; /* run open at chunk start */
         if (c0g >= n) {
             lead_seg[chunk_id] = 0xFFFFFFFFu;
             return;
@@ -2125,7 +2253,6 @@ __global__ __launch_bounds__(SEG_B) void k_seg_emit(
     }
 
     /* Integer ops: the f64 store discipline with exact accumulators. */
-    const uint64_t chunk_id = (uint64_t)blockIdx.x * SEG_B + t;
     if (c0g >= n) {
         lead_seg[chunk_id] = 0xFFFFFFFFu;
         return;
@@ -2137,10 +2264,10 @@ __global__ __launch_bounds__(SEG_B) void k_seg_emit(
         if (OP == 3) return (int64_t)x < a ? (int64_t)x : a;
         return (int64_t)x > a ? (int64_t)x : a;
     };
-    int64_t segid = (int64_t)head_base[(size_t)blockIdx.x * hstride] + excl - 1; /* run open at chunk start */
-    /* Fast path: a fully-distinct interior chunk (the dominant C1 shape)
-     * emits its length-1 runs with pure vector stores — no branches. If its
-     * last run goes on, the next chunk's lead carries the rest. */
+    int64_t segid = tile_base + excl - 1; /* run open at chunk start */
+    /* A fully-distinct interior chunk of a general wave emits its length-1
+     * runs with pure vector stores — no branches. If its last run goes on,
+     * the next chunk's lead carries the rest. */
     if (cnt == SEG_IPT && c0g + SEG_IPT <= n) {
         int64_t s0 = segid + 1;
         int64_t *okp = (int64_t *)out_k + s0;
@@ -2430,8 +2557,9 @@ struct StatsAcc {
     }
 };
 
-/* Sibling of k_seg_emit<OP,PK> for i64 values: same geometry (SEG_B threads x
- * SEG_IPT-row chunks, register-only, 16-B loads), same block-exclusive head
+/* Sibling of k_seg_emit<OP,PK> for i64 values: same tiles and chunks (SEG_B
+ * threads x SEG_IPT-row chunks; still chunk-per-lane 16-B loads and a shuffle
+ * scan, not k_seg_emit's striped loads), same block-exclusive head
  * scan seeded from head_base[blockIdx.x * hstride] — but its own store
  * discipline: runs contained in a chunk are plain-stored, a run open at a
  * chunk start and every chunk's last run are flushed with global atomics —
