@@ -107,4 +107,24 @@ VEGA_INLINE VEGA_HD uint32_t vega_sample_split_cell(uint64_t d, const uint64_t *
     return lo;
 }
 
+/* ---- order of doubles (MIN_F64 / MAX_F64, stats_by_key_f64; DESIGN.md "f64
+ * stats and min/max") ----
+ * ord(b) of a double's bit pattern b, read as a signed i64, is strictly
+ * monotone on non-NaN doubles: -inf < ... < -0.0 < +0.0 < ... < +inf. It is
+ * an involution: ord(ord(b)) == b. min / max of doubles are min / max under
+ * ord, NaN skipped. */
+VEGA_INLINE VEGA_HD uint64_t vega_f64_ord(uint64_t b) {
+    return b ^ ((uint64_t)((int64_t)b >> 63) & 0x7FFFFFFFFFFFFFFFULL);
+}
+/* NaN of either sign, any payload */
+VEGA_INLINE VEGA_HD int vega_f64_bits_nan(uint64_t b) {
+    return (b & 0x7FFFFFFFFFFFFFFFULL) > 0x7FF0000000000000ULL;
+}
+/* ord(b) with NaN replaced by `ident` (INT64_MAX under min, INT64_MIN under
+ * max). No non-NaN double maps to either identity, and ord of an identity is
+ * a NaN bit pattern: an identity that survives a fold un-maps to NaN. */
+VEGA_INLINE VEGA_HD int64_t vega_f64_ord_or(uint64_t b, int64_t ident) {
+    return vega_f64_bits_nan(b) ? ident : (int64_t)vega_f64_ord(b);
+}
+
 #endif /* VEGA_COMMON_H */

@@ -50,6 +50,14 @@ typedef enum {
     VEGA_OP_SUM_F64 = 2,   /* reduce_by_key(+) on f64 (1e-6 rel tolerance) */
     VEGA_OP_MIN_I64 = 3,
     VEGA_OP_MAX_I64 = 4,
+    /* min / max of f64 values (the closures |a, b| a.min(b) / a.max(b)): the
+     * order is that of vega_f64_order_key, so -0.0 < +0.0; NaN values (either
+     * sign, any payload) are skipped; a key whose values are all NaN gets a NaN
+     * of unspecified payload. f64 values required (an i64-valued rdd:
+     * VEGA_ERR_INVALID, as SUM_F64); the result has f64 values. Accepted
+     * wherever SUM_F64 is. */
+    VEGA_OP_MIN_F64 = 5,
+    VEGA_OP_MAX_F64 = 6,
 } vega_op_t;
 
 /* narrow transforms (rdd.rs:199-235 map/filter, pair_rdd.rs:84-101
@@ -198,7 +206,8 @@ int vega_gpu_count_by_value(vega_ctx_t *ctx, vega_rdd_t rdd, uint32_t nparts,
  * values: create |v| (1, v, v, v), merge_value / merge_combiners field-wise
  * +, wrapping +, min, max. One grouping sort and one segmented pass yield all
  * four columns. Input: a plain pair rdd with i64 values, not modified (f64
- * values: VEGA_ERR_UNSUPPORTED; grouped / join-result / stats handles:
+ * values: VEGA_ERR_UNSUPPORTED — vega_gpu_stats_by_key_f64 is their entry;
+ * grouped / join-result / stats handles:
  * VEGA_ERR_INVALID; ngpus > 1 context: VEGA_ERR_UNSUPPORTED). Rows come in
  * grouping order, unspecified as for reduce_by_key.
  * The result is a STATS rdd: keys plus the four columns, collected with
@@ -211,9 +220,34 @@ int vega_gpu_stats_by_key(vega_ctx_t *ctx, vega_rdd_t rdd, uint32_t nparts, vega
 /* keys == NULL queries *nk; all five arrays sized *nk, rows aligned across columns */
 int vega_gpu_collect_stats(vega_ctx_t *ctx, vega_rdd_t stats, int64_t *keys, int64_t *count,
                            int64_t *sum, int64_t *min, int64_t *max, uint64_t *nk);
+/* the same combiner over f64 values: create |v| (1, v, v, v), merge field-wise
+ * +, IEEE +, min, max. count counts every row, NaN rows included. sum is plain
+ * IEEE (NaN propagates, inf + -inf is NaN) in the summation shape of
+ * reduce_by_key(SUM_F64): per key it is bit-identical to that call's value on
+ * the same handle, bit-stable run to run, and no floating-point atomic touches
+ * it. min / max are those of VEGA_OP_MIN_F64 / MAX_F64: the order of
+ * vega_f64_order_key, NaN skipped, NaN for an all-NaN key.
+ * Input: a plain pair rdd with f64 values, not modified (i64 values, grouped /
+ * join-result / stats handles: VEGA_ERR_INVALID; ngpus > 1 context or
+ * n >= 2^32: VEGA_ERR_UNSUPPORTED; n == 0: 0 keys). On any failure no handle
+ * is handed out. The result is a STATS rdd of the f64 kind: the same column
+ * placement (keys, i64 count, then sum / min / max as doubles), so
+ * vega_gpu_count, vega_gpu_free_rdd and an entry unaware of the kind behave as
+ * for vega_gpu_stats_by_key. Collect it with vega_gpu_collect_stats_f64;
+ * each collect entry returns VEGA_ERR_INVALID on the other kind. */
+int vega_gpu_stats_by_key_f64(vega_ctx_t *ctx, vega_rdd_t rdd, uint32_t nparts, vega_rdd_t *out);
+/* keys == NULL queries *nk; all five arrays sized *nk, rows aligned across columns */
+int vega_gpu_collect_stats_f64(vega_ctx_t *ctx, vega_rdd_t stats, int64_t *keys, int64_t *count,
+                               double *sum, double *min, double *max, uint64_t *nk);
+/* ord(b) = b ^ (((int64_t)b >> 63) & 0x7FFFFFFFFFFFFFFF) of a double's bit
+ * pattern b; read as a signed i64 it is strictly monotone on non-NaN doubles
+ * (-inf < ... < -0.0 < +0.0 < ... < +inf) and ord(ord(b)) == b. Pure host
+ * code: needs no GPU and no context. */
+uint64_t vega_f64_order_key(uint64_t bits);
 /* map_values(|c| c.<which>): a PLAIN (key, column) pair rdd, device copy, same
- * row order — usable by every op and action. Not a stats rdd, or a which
- * outside vega_stat_t: VEGA_ERR_INVALID. */
+ * row order — usable by every op and action. Serves both kinds of stats rdd:
+ * COUNT is i64-valued; SUM / MIN / MAX of an f64 stats rdd are f64-valued. Not
+ * a stats rdd, or a which outside vega_stat_t: VEGA_ERR_INVALID. */
 int vega_gpu_stats_column(vega_ctx_t *ctx, vega_rdd_t stats, vega_stat_t which, vega_rdd_t *out);
 
 /* narrow transforms (device-resident; stable order for filter) */
@@ -247,16 +281,18 @@ int vega_gpu_collect_groups(vega_ctx_t *ctx, vega_rdd_t rdd, int64_t *keys,
  * modify the input. A plain element RDD is encoded as in distinct: element
  * in the key column, value column 0. */
 /* reduce (rdd.rs:274-291) with the closure |(k1,v1),(k2,v2)| (k1 op k2,
- * v1 op v2): op in {SUM_I64, SUM_F64, MIN_I64, MAX_I64} applied column-wise.
- * The key column is always i64 (SUM wraps, also under SUM_F64); out_v is
- * int64_t or double per op. Empty rdd: *nonempty = 0 (the reference's None). */
+ * v1 op v2): op in {SUM_I64, SUM_F64, MIN_I64, MAX_I64, MIN_F64, MAX_F64}
+ * applied column-wise. The key column is always i64 (SUM wraps, also under
+ * SUM_F64; MIN_F64 / MAX_F64 take its i64 min / max); out_v is int64_t or
+ * double per op. Empty rdd: *nonempty = 0 (the reference's None). */
 int vega_gpu_reduce(vega_ctx_t *ctx, vega_rdd_t rdd, vega_op_t op, int64_t *out_k,
                     void *out_v, int *nonempty);
 /* fold (rdd.rs:311-322): init seeds every partition's fold and the fold
  * across partitions, so with P = nparts of the handle the result is init
  * combined P+1 times with reduce(rdd) (SUM: reduce + (P+1)*init). An empty
  * rdd folds to init combined P+1 times. aggregate(init, seq, comb) collapses
- * to fold under the fixed op enum. */
+ * to fold under the fixed op enum. init_v is a double for the f64 ops; under
+ * MIN_F64 / MAX_F64 a NaN init is skipped like a NaN value. */
 int vega_gpu_fold(vega_ctx_t *ctx, vega_rdd_t rdd, vega_op_t op, int64_t init_k,
                   const void *init_v, int64_t *out_k, void *out_v);
 /* min / max (rdd.rs:1081-1099): the lexicographic extreme row under Rust's
@@ -376,7 +412,8 @@ int vega_dev_partition_range_i64(void *stream, const int64_t *keys, const int64_
  * with an exact collision cleanup) then one combiner per equal-key run.
  * in_k/in_v are NOT modified. out arrays must hold n rows (worst case
  * all-distinct). *h_nout = #distinct keys (host, after internal sync).
- * vals/out_v are int64 for SUM_I64/COUNT/MIN/MAX, double for SUM_F64. */
+ * vals/out_v are int64 for SUM_I64/COUNT/MIN_I64/MAX_I64, double for SUM_F64 /
+ * MIN_F64 / MAX_F64. */
 int vega_dev_sort_reduce(void *stream, const int64_t *in_k, const void *in_v,
                          uint64_t n, int op, int64_t *out_k, void *out_v,
                          uint64_t *h_nout, void *d_ws, size_t ws_bytes);
@@ -391,6 +428,16 @@ int vega_dev_sort_reduce(void *stream, const int64_t *in_k, const void *in_v,
 int vega_dev_sort_stats_i64(void *stream, const int64_t *in_k, const int64_t *in_v, uint64_t n,
                             int64_t *out_k, int64_t *out_count, int64_t *out_sum,
                             int64_t *out_min, int64_t *out_max, uint64_t *h_nout,
+                            void *d_ws, size_t ws_bytes);
+
+/* vega_dev_sort_stats_i64 for f64 values: the aggregate of
+ * vega_gpu_stats_by_key_f64, same contract. in_k/in_v are NOT modified. The
+ * five out arrays must hold n rows each and be 16-byte aligned, else
+ * VEGA_ERR_INVALID. d_ws must hold vega_dev_ws_bytes(n) bytes, else
+ * VEGA_ERR_CAP. *h_nout = #distinct keys (host, after an internal sync). */
+int vega_dev_sort_stats_f64(void *stream, const int64_t *in_k, const double *in_v, uint64_t n,
+                            int64_t *out_k, int64_t *out_count, double *out_sum,
+                            double *out_min, double *out_max, uint64_t *h_nout,
                             void *d_ws, size_t ws_bytes);
 
 /* diagnostic: the grouped rows (equal keys adjacent) that vega_dev_sort_reduce
@@ -481,7 +528,7 @@ int vega_dev_select_k_i64(void *stream, const int64_t *keys, const int64_t *vals
                           int64_t *out_k, int64_t *out_v, uint64_t *h_nout, int *h_passes,
                           void *d_ws, size_t ws_bytes);
 /* column-wise reduce of n >= 1 device rows to one HOST row (the op set of
- * vega_gpu_reduce; vals / h_out_v are double for SUM_F64). d_ws: 64 KiB
+ * vega_gpu_reduce; vals / h_out_v are double for the f64 ops). d_ws: 64 KiB
  * suffices (VEGA_ERR_CAP if too small). */
 int vega_dev_reduce_pairs(void *stream, const int64_t *keys, const void *vals, uint64_t n,
                           int op, int64_t *h_out_k, void *h_out_v, void *d_ws,

@@ -23,6 +23,11 @@
 
 using namespace vega;
 
+/* the ops whose values (input and result) are doubles */
+static bool op_is_f64(int op) {
+    return op == VEGA_OP_SUM_F64 || op == VEGA_OP_MIN_F64 || op == VEGA_OP_MAX_F64;
+}
+
 struct RddImpl {
     uint64_t n = 0;
     int vtype = 0; /* 0 = i64 vals, 1 = f64 vals */
@@ -40,6 +45,7 @@ struct RddImpl {
      * column, d_v2 = sum, d_min / d_max the other two — an entry that never
      * looks at the kind sees a valid (key, count) pair rdd of n rows */
     bool stats = false;
+    bool stats_f64 = false; /* stats_by_key_f64: sum / min / max hold doubles */
     void *d_min = nullptr;
     void *d_max = nullptr;
     /* outer join result (vega_gpu_join_kind 1-3): d_k / d_v / d_v2 as a join
@@ -330,7 +336,7 @@ int vega_gpu_gen_rdd_uniform(vega_ctx_t *c, uint64_t n, uint64_t seed, int key_b
 static int reduce_multi(vega_ctx *c, RddImpl *r, int op, uint32_t nparts,
                         vega_rdd_t *out) {
     const int G = c->ngpus;
-    if ((op == VEGA_OP_SUM_F64) && r->vtype != 1) return VEGA_ERR_INVALID;
+    if (op_is_f64(op) && r->vtype != 1) return VEGA_ERR_INVALID;
     /* per-device partition into G buckets */
     std::vector<int64_t *> pk(G, nullptr), pv(G, nullptr);
     std::vector<std::vector<uint64_t>> counts(G, std::vector<uint64_t>(G, 0));
@@ -391,7 +397,7 @@ static int reduce_multi(vega_ctx *c, RddImpl *r, int op, uint32_t nparts,
     std::vector<uint64_t> alloc_out(G);
     for (int p = 0; p < G; ++p) alloc_out[p] = rn[p] ? rn[p] : 1;
     RddImpl *o;
-    int rc = new_mrdd(c, alloc_out, op == VEGA_OP_SUM_F64 ? 1 : 0, nparts, &o, out);
+    int rc = new_mrdd(c, alloc_out, op_is_f64(op) ? 1 : 0, nparts, &o, out);
     if (rc) return rc;
     uint64_t total = 0;
     for (int p = 0; p < G; ++p) {
@@ -424,13 +430,13 @@ static int reduce_common(vega_ctx *c, vega_rdd_t rdd, int op, uint32_t nparts,
     RddImpl *r = get_rdd(c, rdd);
     if (!r) return VEGA_ERR_INVALID;
     if (c->ngpus > 1) return reduce_multi(c, r, op, nparts, out);
-    /* SUM_F64 needs f64 values; COUNT ignores values; the i64 ops need i64 */
-    if (op == VEGA_OP_SUM_F64 && r->vtype != 1) return VEGA_ERR_INVALID;
-    if (op != VEGA_OP_SUM_F64 && op != VEGA_OP_COUNT && r->vtype == 1) return VEGA_ERR_INVALID;
+    /* the f64 ops need f64 values; COUNT ignores values; the i64 ops need i64 */
+    if (op_is_f64(op) && r->vtype != 1) return VEGA_ERR_INVALID;
+    if (!op_is_f64(op) && op != VEGA_OP_COUNT && r->vtype == 1) return VEGA_ERR_INVALID;
     int rc = ensure_ws(c, r->n);
     if (rc) return rc;
     RddImpl *o;
-    rc = new_rdd(c, r->n ? r->n : 1, op == VEGA_OP_SUM_F64 ? 1 : 0, nparts, &o, out);
+    rc = new_rdd(c, r->n ? r->n : 1, op_is_f64(op) ? 1 : 0, nparts, &o, out);
     if (rc) return rc;
     Ws ws(c->ws, c->ws_bytes);
     uint64_t nout = 0;
@@ -1153,10 +1159,10 @@ static int reduce_rows(vega_ctx *c, RddImpl *r, int op, int64_t *out_k, void *ou
     return VEGA_OK;
 }
 
-/* the reduce_common type guards: SUM_F64 needs f64 values, the i64 ops need
- * i64 values, COUNT is not a reduce closure */
+/* the reduce_common type guards: the f64 ops need f64 values, the i64 ops
+ * need i64 values, COUNT is not a reduce closure */
 static bool action_op_ok(const RddImpl *r, int op) {
-    if (op == VEGA_OP_SUM_F64) return r->vtype == 1;
+    if (op_is_f64(op)) return r->vtype == 1;
     if (op == VEGA_OP_SUM_I64 || op == VEGA_OP_MIN_I64 || op == VEGA_OP_MAX_I64)
         return r->vtype == 0;
     return false;
@@ -1194,7 +1200,7 @@ int vega_gpu_fold(vega_ctx_t *c, vega_rdd_t rdd, vega_op_t op, int64_t init_k,
     memcpy(&iv, init_v, 8);
     if (op == VEGA_OP_SUM_I64 || op == VEGA_OP_SUM_F64)
         *out_k = (int64_t)((uint64_t)rk + times * (uint64_t)init_k);
-    else if (op == VEGA_OP_MIN_I64)
+    else if (op == VEGA_OP_MIN_I64 || op == VEGA_OP_MIN_F64)
         *out_k = have && rk < init_k ? rk : init_k;
     else
         *out_k = have && rk > init_k ? rk : init_k;
@@ -1209,6 +1215,17 @@ int vega_gpu_fold(vega_ctx_t *c, vega_rdd_t rdd, vega_op_t op, int64_t init_k,
         if (!have) { acc = init; left--; }
         for (uint64_t i = 0; i < left; ++i) acc += init;
         memcpy(out_v, &acc, 8);
+    } else if (op == VEGA_OP_MIN_F64 || op == VEGA_OP_MAX_F64) {
+        /* min / max under vega_f64_ord, NaN skipped on either side: combining
+         * init any number of times is combining it once; a NaN init loses to
+         * any number, and NaN comes out only when both sides are NaN */
+        const bool mx = op == VEGA_OP_MAX_F64;
+        const int64_t ident = mx ? INT64_MIN : INT64_MAX;
+        const int64_t oi = vega_f64_ord_or((uint64_t)iv, ident);
+        const int64_t orr = have ? vega_f64_ord_or(rv, ident) : ident;
+        uint64_t o = (uint64_t)iv;
+        if (mx ? (orr > oi) : (orr < oi)) o = rv;
+        memcpy(out_v, &o, 8);
     } else {
         int64_t red = (int64_t)rv, o;
         if (op == VEGA_OP_MIN_I64) o = have && red < iv ? red : iv;
@@ -1370,11 +1387,12 @@ int vega_gpu_stats_by_key(vega_ctx_t *c, vega_rdd_t rdd, uint32_t nparts, vega_r
     return VEGA_OK;
 }
 
-int vega_gpu_collect_stats(vega_ctx_t *c, vega_rdd_t stats, int64_t *keys, int64_t *count,
-                           int64_t *sum, int64_t *min, int64_t *max, uint64_t *nk) {
+/* collect of either kind of stats rdd: the five columns are 8-byte words */
+static int collect_stats_common(vega_ctx *c, vega_rdd_t stats, bool f64, int64_t *keys,
+                                int64_t *count, void *sum, void *min, void *max, uint64_t *nk) {
     if (!c || !nk) return VEGA_ERR_INVALID;
     RddImpl *r = get_rdd(c, stats);
-    if (!r || !r->stats) return VEGA_ERR_INVALID;
+    if (!r || !r->stats || r->stats_f64 != f64) return VEGA_ERR_INVALID; /* the other kind's entry */
     if (!keys) { *nk = r->n; return VEGA_OK; }
     if (*nk < r->n) return VEGA_ERR_CAP;
     *nk = r->n;
@@ -1391,6 +1409,66 @@ int vega_gpu_collect_stats(vega_ctx_t *c, vega_rdd_t stats, int64_t *keys, int64
     return VEGA_OK;
 }
 
+int vega_gpu_collect_stats(vega_ctx_t *c, vega_rdd_t stats, int64_t *keys, int64_t *count,
+                           int64_t *sum, int64_t *min, int64_t *max, uint64_t *nk) {
+    return collect_stats_common(c, stats, false, keys, count, sum, min, max, nk);
+}
+
+/* the f64 combiner: C = (count, sum, min, max) over f64 values — IEEE sum in
+ * the summation shape of reduce_by_key(SUM_F64), min / max under vega_f64_ord
+ * with NaN skipped (vega_gpu.h). One grouping sort, one segmented pass. */
+int vega_gpu_stats_by_key_f64(vega_ctx_t *c, vega_rdd_t rdd, uint32_t nparts, vega_rdd_t *out) {
+    if (!c || !out) return VEGA_ERR_INVALID;
+    if (c->ngpus > 1) return VEGA_ERR_UNSUPPORTED; /* G>1: north-star ops only */
+    RddImpl *r = get_rdd(c, rdd);
+    if (!r || r->grouped || r->stats || r->d_v2) return VEGA_ERR_INVALID; /* plain pair handles only */
+    if (r->vtype != 1) {
+        snprintf(c->err, sizeof c->err,
+                 "stats_by_key_f64: i64 values (use vega_gpu_stats_by_key)");
+        return VEGA_ERR_INVALID;
+    }
+    if (r->n >= (1ULL << 32)) {
+        snprintf(c->err, sizeof c->err,
+                 "stats_by_key_f64 on %llu rows exceeds the 2^32-1 per-call limit",
+                 (unsigned long long)r->n);
+        return VEGA_ERR_UNSUPPORTED;
+    }
+    int rc = ensure_ws(c, r->n);
+    if (rc) return rc;
+    RddImpl *o;
+    rc = new_rdd(c, r->n ? r->n : 1, 0, nparts, &o, out);
+    if (rc) return rc;
+    o->stats = true;
+    o->stats_f64 = true;
+    const size_t bytes = (size_t)(r->n ? r->n : 1) * 8;
+    Ws ws(c->ws, c->ws_bytes);
+    uint64_t nout = 0;
+    hipError_t e = hipMalloc(&o->d_v2, bytes);
+    if (e == hipSuccess) e = hipMalloc(&o->d_min, bytes);
+    if (e == hipSuccess) e = hipMalloc(&o->d_max, bytes);
+    if (e == hipSuccess)
+        e = group_sort_stats_f64(c->stream, (const uint64_t *)r->d_k, (const uint64_t *)r->d_v,
+                                 r->n, o->d_k, (int64_t *)o->d_v, (double *)o->d_v2,
+                                 (double *)o->d_min, (double *)o->d_max, &nout, ws);
+    if (e != hipSuccess) { /* no half-built handle is handed out */
+        vega_gpu_free_rdd(c, *out);
+        *out = 0;
+        snprintf(c->err, sizeof c->err, "stats_by_key_f64: %s", hipGetErrorString(e));
+        if (e == hipErrorNotSupported) return VEGA_ERR_UNSUPPORTED;
+        return e == hipErrorOutOfMemory ? VEGA_ERR_NOMEM : VEGA_ERR_HIP;
+    }
+    o->n = nout;
+    return VEGA_OK;
+}
+
+int vega_gpu_collect_stats_f64(vega_ctx_t *c, vega_rdd_t stats, int64_t *keys, int64_t *count,
+                               double *sum, double *min, double *max, uint64_t *nk) {
+    return collect_stats_common(c, stats, true, keys, count, sum, min, max, nk);
+}
+
+/* the order key of a double's bit pattern (vega_common.h). Pure host code. */
+uint64_t vega_f64_order_key(uint64_t bits) { return vega_f64_ord(bits); }
+
 /* map_values(|c| c.<which>): a plain (key, column) pair rdd, device copy */
 int vega_gpu_stats_column(vega_ctx_t *c, vega_rdd_t stats, vega_stat_t which, vega_rdd_t *out) {
     if (!c || !out) return VEGA_ERR_INVALID;
@@ -1405,7 +1483,9 @@ int vega_gpu_stats_column(vega_ctx_t *c, vega_rdd_t stats, vega_stat_t which, ve
     default: return VEGA_ERR_INVALID;
     }
     RddImpl *o;
-    int rc = new_rdd(c, r->n ? r->n : 1, 0, r->nparts, &o, out);
+    /* the count is i64 in both kinds; sum / min / max follow the kind */
+    const int vtype = (r->stats_f64 && (int)which != VEGA_STAT_COUNT) ? 1 : 0;
+    int rc = new_rdd(c, r->n ? r->n : 1, vtype, r->nparts, &o, out);
     if (rc) return rc;
     o->n = r->n;
     if (r->n) {
@@ -1794,6 +1874,29 @@ int vega_dev_sort_stats_i64(void *stream, const int64_t *in_k, const int64_t *in
     return e == hipSuccess ? VEGA_OK : (e == hipErrorOutOfMemory ? VEGA_ERR_NOMEM : VEGA_ERR_HIP);
 }
 
+/* vega_dev_sort_stats_i64 for f64 values; see vega_gpu.h */
+int vega_dev_sort_stats_f64(void *stream, const int64_t *in_k, const double *in_v, uint64_t n,
+                            int64_t *out_k, int64_t *out_count, double *out_sum,
+                            double *out_min, double *out_max, uint64_t *h_nout,
+                            void *d_ws, size_t ws_bytes) {
+    if (!h_nout) return VEGA_ERR_INVALID;
+    *h_nout = 0;
+    if (n >= (1ULL << 32)) return VEGA_ERR_UNSUPPORTED;
+    if (!n) return VEGA_OK;
+    if (!in_k || !in_v || !out_k || !out_count || !out_sum || !out_min || !out_max)
+        return VEGA_ERR_INVALID;
+    if ((((uintptr_t)out_k | (uintptr_t)out_count | (uintptr_t)out_sum |
+          (uintptr_t)out_min | (uintptr_t)out_max) & 15) != 0)
+        return VEGA_ERR_INVALID;
+    if (!d_ws || ws_bytes < ws_bytes_for(n)) return VEGA_ERR_CAP;
+    Ws ws(d_ws, ws_bytes);
+    hipError_t e = group_sort_stats_f64((hipStream_t)stream, (const uint64_t *)in_k,
+                                        (const uint64_t *)in_v, n, out_k, out_count, out_sum,
+                                        out_min, out_max, h_nout, ws);
+    if (e == hipErrorNotSupported) return VEGA_ERR_UNSUPPORTED;
+    return e == hipSuccess ? VEGA_OK : (e == hipErrorOutOfMemory ? VEGA_ERR_NOMEM : VEGA_ERR_HIP);
+}
+
 int vega_dev_sort_pairs_i64(void *stream, int64_t *keys, int64_t *vals, uint64_t n,
                             void *d_ws, size_t ws_bytes) {
     Ws ws(d_ws, ws_bytes);
@@ -1905,7 +2008,7 @@ int vega_dev_reduce_pairs(void *stream, const int64_t *keys, const void *vals, u
                           int64_t *h_out_k, void *h_out_v, void *d_ws, size_t ws_bytes) {
     if (!n || !keys || !vals || !h_out_k || !h_out_v) return VEGA_ERR_INVALID;
     if (op != VEGA_OP_SUM_I64 && op != VEGA_OP_SUM_F64 && op != VEGA_OP_MIN_I64 &&
-        op != VEGA_OP_MAX_I64)
+        op != VEGA_OP_MAX_I64 && op != VEGA_OP_MIN_F64 && op != VEGA_OP_MAX_F64)
         return VEGA_ERR_INVALID;
     Ws ws(d_ws, ws_bytes);
     hipError_t e = col_reduce((hipStream_t)stream, keys, vals, n, op, h_out_k, h_out_v, ws);

@@ -67,12 +67,15 @@ hipError_t group_sort_u64(hipStream_t s, const uint64_t *in_k, const uint64_t *i
                           int want_packed, int *out_packed, Ws &ws,
                           const uint64_t **res_k, const uint64_t **res_v,
                           int route = 0, int *route_taken = nullptr,
-                          const uint32_t **fin_heads = nullptr);
+                          const uint32_t **fin_heads = nullptr,
+                          void **idle = nullptr, size_t *idle_bytes = nullptr);
 /* *fin_heads (optional out): run-head counts per 2048-row tile that the bucket
  * finish kept while it stored the rows, for seg_reduce / seg_stats — non-null
  * only when the finish route produced the result (not after its error flag,
  * not on the four-pass route, narrow keys, joins or cogroup). The buffer is
- * carved from ws and is consumed (scanned in place) by its one user. */
+ * carved from ws and is consumed (scanned in place) by its one user.
+ * *idle / *idle_bytes (optional out): the sort's ping-pong buffer that does
+ * not hold the result (n * 16 bytes of ws), free for the caller to reuse. */
 
 /* rows per occupied hash bucket that group_sort_u64's automatic route
  * estimates from its key sample (host arithmetic only; ns <= 2048) */
@@ -85,7 +88,7 @@ hipError_t group_rows(hipStream_t s, const uint64_t *in_k, const uint64_t *in_v,
                       int route, uint64_t *out_k, uint64_t *out_v, Ws &ws, int *route_taken);
 
 /* segmented aggregate over key-sorted rows: one output row per equal-key
- * run. op: VEGA_OP_*. Returns #segments in *h_nout (after stream sync).
+ * run. op: VEGA_OP_* (0..6). Returns #segments in *h_nout (after stream sync).
  * out_k / out_v need no initialising: every slot is plain-stored.
  * fin_heads: group_sort_u64's per-tile head counts, or nullptr to count. */
 hipError_t seg_reduce(hipStream_t s, const uint64_t *k, const void *v, uint64_t n,
@@ -112,6 +115,25 @@ hipError_t group_sort_stats(hipStream_t s, const uint64_t *in_k, const uint64_t 
                             uint64_t n, int64_t *out_k, int64_t *out_count,
                             int64_t *out_sum, int64_t *out_min, int64_t *out_max,
                             uint64_t *h_nout, Ws &ws);
+
+/* the f64 combiner: per equal-key run one row of (key, count, IEEE sum, min,
+ * max) over f64 values v, min / max under vega_f64_ord with NaN skipped
+ * (vega_common.h). The sum has the summation shape of seg_reduce's SUM_F64:
+ * the same rows give the same bits. No output slot needs initialising.
+ * spare / spare_bytes: a device buffer the caller no longer needs, used for
+ * the lead arrays that do not fit what is left of ws (may be null). Returns
+ * #segments in *h_nout (after stream sync). */
+hipError_t seg_stats_f64(hipStream_t s, const uint64_t *k, const uint64_t *v, uint64_t n,
+                         int64_t *out_k, int64_t *out_count, double *out_sum,
+                         double *out_min, double *out_max, uint64_t *h_nout, Ws &ws,
+                         bool packed = false, const uint32_t *fin_heads = nullptr,
+                         void *spare = nullptr, size_t spare_bytes = 0);
+
+/* grouping sort (as group_sort_reduce runs it) + seg_stats_f64 */
+hipError_t group_sort_stats_f64(hipStream_t s, const uint64_t *in_k, const uint64_t *in_v,
+                                uint64_t n, int64_t *out_k, int64_t *out_count,
+                                double *out_sum, double *out_min, double *out_max,
+                                uint64_t *h_nout, Ws &ws);
 
 /* hash-mod partition scatter; h_counts on host after sync */
 hipError_t hash_partition(hipStream_t s, const uint64_t *in_k, const uint64_t *in_v,
@@ -197,7 +219,7 @@ hipError_t cogroup_index(hipStream_t s, const int64_t *ka_u, uint64_t nka,
 
 /* ---- device-side actions (rdd.rs reduce/fold/min/max/top/take_ordered) ---- */
 
-/* col_reduce ops: the vega_op_t values 0/2/3/4 applied COLUMN-WISE (key
+/* col_reduce ops: the vega_op_t values 0/2/3/4/5/6 applied COLUMN-WISE (key
  * column always i64), plus the lexicographic extreme row under (i64, i64) */
 enum { COLRED_LEXMIN = 100, COLRED_LEXMAX = 101 };
 

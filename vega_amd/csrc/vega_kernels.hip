@@ -1728,14 +1728,20 @@ __global__ void k_unpack_rows(const uint64_t *pk, uint64_t n, uint64_t *k, uint6
  * tile, ceil(n / FIN_FT) entries at the front of a buffer of 2 * nb + 1 (the
  * shape seg_reduce scans). Set only when the finish produced the result; on
  * every other route, and after the finish's flag (some tiles then hold no
- * count), it is nullptr and the caller counts heads itself. */
+ * count), it is nullptr and the caller counts heads itself.
+ * *idle / *idle_bytes (optional): the ping-pong buffer that does NOT hold the
+ * result, n * 16 bytes of ws the caller may reuse once this has returned
+ * (nullptr / 0 for n <= 1, where nothing is taken). */
 hipError_t group_sort_u64(hipStream_t s, const uint64_t *in_k, const uint64_t *in_v,
                           uint64_t n, int force_hbytes, int *order_tag,
                           int want_packed, int *out_packed, Ws &ws,
                           const uint64_t **res_k, const uint64_t **res_v,
-                          int route, int *route_taken, const uint32_t **fin_heads) {
+                          int route, int *route_taken, const uint32_t **fin_heads,
+                          void **idle, size_t *idle_bytes) {
     *res_k = in_k;
     *res_v = in_v;
+    if (idle) *idle = nullptr;
+    if (idle_bytes) *idle_bytes = 0;
     if (out_packed) *out_packed = 0;
     if (order_tag) *order_tag = 0;
     if (route_taken) *route_taken = 0;
@@ -1766,6 +1772,12 @@ hipError_t group_sort_u64(hipStream_t s, const uint64_t *in_k, const uint64_t *i
         return hipErrorOutOfMemory;
     HIP_TRY(hipMemsetAsync(d_abort, 0, 4, s));
     HIP_TRY(hipMemsetAsync(desc, 0, (size_t)nb * 256 * 8, s));
+    /* the ping-pong buffer that does not hold the result (either, when the
+     * rows were left in in_k); called where *res_k is final */
+    auto report_idle = [&]() {
+        if (idle) *idle = (*res_k == pA) ? (void *)pB : (void *)pA;
+        if (idle_bytes) *idle_bytes = (size_t)n * 16;
+    };
     int ptag_ctr = 0;
     /* strict order (full (h32,key) lex within runs) only when a caller will
      * binary-search the result (joins/cogroup: force_hbytes or order_tag);
@@ -1847,6 +1859,7 @@ hipError_t group_sort_u64(hipStream_t s, const uint64_t *in_k, const uint64_t *i
             int ab = 0;
             HIP_TRY(hipMemcpyAsync(&ab, d_abort, 4, hipMemcpyDeviceToHost, s));
             HIP_TRY(hipStreamSynchronize(s));
+            report_idle();
             return ab ? hipErrorUnknown : hipSuccess;
         }
         /* sample lied; fall through to the hash path */
@@ -1899,6 +1912,7 @@ hipError_t group_sort_u64(hipStream_t s, const uint64_t *in_k, const uint64_t *i
             if (fin_heads) *fin_heads = fh_d; /* every tile stored its count */
             *res_k = pB;
             *res_v = nullptr;
+            report_idle();
             return hipSuccess;
         }
         /* a bucket or dirty run over its cap: the four passes below start
@@ -1956,6 +1970,7 @@ hipError_t group_sort_u64(hipStream_t s, const uint64_t *in_k, const uint64_t *i
     if (order_tag && !err) *order_tag = (hbytes == 4) ? 4 : 0;
     *res_k = cur_k;
     *res_v = cur_v;
+    report_idle();
     return hipSuccess;
 }
 
@@ -1986,7 +2001,10 @@ __global__ void k_head_count(const uint64_t *k, uint64_t n, uint32_t *hc) {
     }
 }
 
-/* OP: 0 SUM_I64, 1 COUNT, 2 SUM_F64, 3 MIN_I64, 4 MAX_I64.
+/* OP: 0 SUM_I64, 1 COUNT, 2 SUM_F64, 3 MIN_I64, 4 MAX_I64, 5 MIN_F64,
+ * 6 MAX_F64 (the integer discipline of 3 / 4 on vega_f64_ord of the values,
+ * NaN mapped to the op's identity; every slot is stored un-mapped, as double
+ * bits, and k_seg_lead_fold_f64 folds the mapped leads into them).
  * Each thread owns one SEG_IPT-row chunk, each wave the SEG_SPAN rows of its
  * 64 chunks. A wave loads its span STRIPED: every load instruction reads
  * 1 KiB of consecutive rows, 16 B per lane (chunk-per-lane loads touched 64
@@ -2257,12 +2275,21 @@ __global__ __launch_bounds__(SEG_B) void k_seg_emit(
         lead_seg[chunk_id] = 0xFFFFFFFFu;
         return;
     }
-    constexpr int64_t IDENT = (OP == 3) ? INT64_MAX : (OP == 4) ? INT64_MIN : 0;
+    constexpr int64_t IDENT = (OP == 3 || OP == 5) ? INT64_MAX : (OP == 4 || OP == 6) ? INT64_MIN : 0;
     auto fold = [](int64_t a, uint64_t x) -> int64_t {
+        if (OP == 5 || OP == 6) {
+            const int64_t o = vega_f64_ord_or(x, IDENT);
+            return (OP == 5) ? (o < a ? o : a) : (o > a ? o : a);
+        }
         if (OP == 0) return (int64_t)((uint64_t)a + x);
         if (OP == 1) return a + 1;
         if (OP == 3) return (int64_t)x < a ? (int64_t)x : a;
         return (int64_t)x > a ? (int64_t)x : a;
+    };
+    /* what a slot holds: the accumulator, un-mapped for the f64 orders (a
+     * length-1 run's slot, stored raw above, is the same thing) */
+    auto fin = [](int64_t a) -> int64_t {
+        return (OP == 5 || OP == 6) ? (int64_t)vega_f64_ord((uint64_t)a) : a;
     };
     int64_t segid = tile_base + excl - 1; /* run open at chunk start */
     /* A fully-distinct interior chunk of a general wave emits its length-1
@@ -2300,7 +2327,7 @@ __global__ __launch_bounds__(SEG_B) void k_seg_emit(
         if (gi < n) {
             uint64_t pk = (j > 0) ? kk[j - 1] : prev;
             if (gi == 0 || kk[j] != pk) {
-                if (seen) ((int64_t *)out_vv)[segid] = acc; /* interior run: complete */
+                if (seen) ((int64_t *)out_vv)[segid] = fin(acc); /* interior run: complete */
                 segid++;
                 out_k[segid] = (int64_t)kk[j];
                 acc = IDENT;
@@ -2312,7 +2339,7 @@ __global__ __launch_bounds__(SEG_B) void k_seg_emit(
     }
     /* last run started here: what it has so far; k_seg_lead_fold adds the
      * leads of the chunks it runs on into */
-    if (seen) ((int64_t *)out_vv)[segid] = acc;
+    if (seen) ((int64_t *)out_vv)[segid] = fin(acc);
     /* row c0g is valid: it is either a head (cnt counts it first) or the lead */
     if (c0g != 0 && kk[0] == prev) {
         lead_seg[chunk_id] = (uint32_t)open_seg;
@@ -2369,6 +2396,69 @@ __global__ __launch_bounds__(BLOCK) void k_seg_lead_fold(
                 else if (OP == 3) atomicMin((long long *)(out_v + sg), (long long)acc);
                 else atomicMax((long long *)(out_v + sg), (long long)acc);
             }
+        }
+    }
+}
+
+/* min (MAXOP: max) of a slot that holds DOUBLE BITS with a lead accumulated
+ * under vega_f64_ord (NaN rows already mapped to the identity). The slot is
+ * compared under the same order and replaced by compare-and-swap only when the
+ * lead improves it — an integer atomic; a slot holding NaN (a run of NaN so
+ * far) counts as the identity. Min and max are exact in any order, and no
+ * non-NaN double maps to an identity, so an all-NaN run keeps its NaN. */
+template <bool MAXOP>
+__device__ __forceinline__ void f64_slot_extreme(uint64_t *slot, int64_t lead) {
+    constexpr int64_t IDENT = MAXOP ? INT64_MIN : INT64_MAX;
+    if (lead == IDENT) return;
+    unsigned long long old = __hip_atomic_load((unsigned long long *)slot, __ATOMIC_RELAXED,
+                                               __HIP_MEMORY_SCOPE_AGENT);
+    for (;;) {
+        const int64_t o = vega_f64_ord_or(old, IDENT);
+        if (MAXOP ? (lead <= o) : (lead >= o)) return;
+        const unsigned long long seen =
+            atomicCAS((unsigned long long *)slot, old, (unsigned long long)vega_f64_ord((uint64_t)lead));
+        if (seen == old) return;
+        old = seen;
+    }
+}
+
+/* k_seg_lead_fold for OP 5 / 6: the leads are vega_f64_ord values, the slots
+ * double bits (f64_slot_extreme) */
+template <int OP>
+__global__ __launch_bounds__(BLOCK) void k_seg_lead_fold_f64(
+    const uint32_t *__restrict__ lead_seg, const int64_t *__restrict__ lead_part,
+    uint64_t nchunks, uint64_t *__restrict__ out_v) {
+    const int lane = threadIdx.x & 63;
+    constexpr int U = SEG_FOLD_U;
+    constexpr int64_t IDENT = (OP == 5) ? INT64_MAX : INT64_MIN;
+    const uint64_t stride = (uint64_t)gridDim.x * BLOCK * U;
+    /* block-uniform trip count: every lane takes part in the shuffles */
+    for (uint64_t c0 = (uint64_t)blockIdx.x * BLOCK * U; c0 < nchunks; c0 += stride) {
+        uint32_t sgs[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const uint64_t c = c0 + (uint64_t)u * BLOCK + threadIdx.x;
+            sgs[u] = (c < nchunks) ? lead_seg[c] : 0xFFFFFFFFu;
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const uint64_t c = c0 + (uint64_t)u * BLOCK + threadIdx.x;
+            const uint32_t sg = sgs[u];
+            const bool have = sg != 0xFFFFFFFFu;
+            if (!__any(have)) continue;
+            int64_t acc = have ? lead_part[c] : IDENT;
+            long long sid = have ? (long long)sg : -(long long)(lane + 2);
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1) {
+                long long s2 = __shfl_up(sid, off);
+                long long a2 = __shfl_up((long long)acc, off);
+                if (lane >= off && s2 == sid) {
+                    if (OP == 5) acc = (int64_t)a2 < acc ? (int64_t)a2 : acc;
+                    else acc = (int64_t)a2 > acc ? (int64_t)a2 : acc;
+                }
+            }
+            long long snext = __shfl_down(sid, 1);
+            if (have && (lane == 63 || snext != sid)) f64_slot_extreme<OP == 6>(out_v + sg, acc);
         }
     }
 }
@@ -2444,7 +2534,7 @@ hipError_t seg_reduce(hipStream_t s, const uint64_t *k, const void *v, uint64_t 
                       bool packed, const uint32_t *fin_heads) {
     if (n == 0) { *h_nout = 0; return hipSuccess; }
     if (n >= (1ULL << 32)) return hipErrorNotSupported; /* u32 head scan limit */
-    if (op < 0 || op > 4) return hipErrorInvalidValue;
+    if (op < 0 || op > 6) return hipErrorInvalidValue;
     uint32_t nb = nblocks_for(n);
     uint64_t nchunks = (uint64_t)nb * SEG_B;
     uint32_t *lead_seg = (uint32_t *)ws.take(nchunks * 4);
@@ -2470,6 +2560,10 @@ hipError_t seg_reduce(hipStream_t s, const uint64_t *k, const void *v, uint64_t 
         case 7: SEG_LAUNCH(3, true); break;
         case 8: SEG_LAUNCH(4, false); break;
         case 9: SEG_LAUNCH(4, true); break;
+        case 10: SEG_LAUNCH(5, false); break;
+        case 11: SEG_LAUNCH(5, true); break;
+        case 12: SEG_LAUNCH(6, false); break;
+        case 13: SEG_LAUNCH(6, true); break;
         default: return hipErrorInvalidValue;
         }
 #undef SEG_LAUNCH
@@ -2496,6 +2590,14 @@ hipError_t seg_reduce(hipStream_t s, const uint64_t *k, const void *v, uint64_t 
         case 3:
             hipLaunchKernelGGL((k_seg_lead_fold<3>), dim3(gb), dim3(BLOCK), 0, s, lead_seg, lp,
                                nchunks, (int64_t *)out_v);
+            break;
+        case 5:
+            hipLaunchKernelGGL((k_seg_lead_fold_f64<5>), dim3(gb), dim3(BLOCK), 0, s, lead_seg, lp,
+                               nchunks, (uint64_t *)out_v);
+            break;
+        case 6:
+            hipLaunchKernelGGL((k_seg_lead_fold_f64<6>), dim3(gb), dim3(BLOCK), 0, s, lead_seg, lp,
+                               nchunks, (uint64_t *)out_v);
             break;
         default:
             hipLaunchKernelGGL((k_seg_lead_fold<4>), dim3(gb), dim3(BLOCK), 0, s, lead_seg, lp,
@@ -2783,6 +2885,339 @@ hipError_t group_sort_stats(hipStream_t s, const uint64_t *in_k, const uint64_t 
     if (e != hipSuccess) return e;
     return seg_stats(s, sk, sv, n, out_k, out_count, out_sum, out_min, out_max, h_nout, ws,
                      pk != 0, fh);
+}
+
+/* ------------------------------------------------------------------ */
+/* the f64 combiner: C = (count, sum, min, max) over f64 values         */
+
+/* count, sequential IEEE sum from 0.0, and min / max under vega_f64_ord with
+ * NaN rows skipped (mapped to the identities) */
+struct StatsAccF64 {
+    uint32_t cnt;
+    double sum;
+    int64_t mn, mx;
+    __device__ __forceinline__ void reset() { cnt = 0; sum = 0.0; mn = INT64_MAX; mx = INT64_MIN; }
+    __device__ __forceinline__ void add(uint64_t b) {
+        cnt += 1;
+        sum += __longlong_as_double((long long)b);
+        const int64_t lo = vega_f64_ord_or(b, INT64_MAX), hi = vega_f64_ord_or(b, INT64_MIN);
+        mn = lo < mn ? lo : mn;
+        mx = hi > mx ? hi : mx;
+    }
+};
+
+/* k_seg_stats's tiles, chunks, loads and head scan with k_seg_emit's store
+ * discipline, for f64 values: no atomics in this kernel and no output slot
+ * needs initialising. The chunk that holds a run's head plain-stores the key
+ * and the four fields accumulated inside that chunk — min / max un-mapped, as
+ * double bits; a NaN-only part stores the NaN the identity un-maps to. The
+ * rows before a chunk's first head are its lead and go to (lead_seg,
+ * lead_cnt, lead_sum, lead_min, lead_max)[chunk], lead_seg written for every
+ * chunk (0xFFFFFFFF: none); min / max leads stay under vega_f64_ord.
+ * k_stats_f64_fold then folds count, min and max into the slots and
+ * k_f64_seg_combine the sums.
+ * The sum has the summation shape of k_seg_emit<2>: per chunk a sequential sum
+ * from 0.0 (a length-1 run stores 0.0 + x), the head's chunk stores the base,
+ * the later chunks' leads are summed in chunk order from 0.0 by the same
+ * k_f64_seg_combine and added to it. Same rows, same bits. */
+template <bool PK>
+__global__ __launch_bounds__(SEG_B) void k_seg_stats_f64(
+    const uint64_t *__restrict__ k, const uint64_t *__restrict__ v, uint64_t n,
+    const uint32_t *__restrict__ head_base, uint32_t hstride,
+    int64_t *__restrict__ out_k, int64_t *__restrict__ out_count,
+    double *__restrict__ out_sum, uint64_t *__restrict__ out_min,
+    uint64_t *__restrict__ out_max, uint32_t *__restrict__ lead_seg,
+    uint32_t *__restrict__ lead_cnt, double *__restrict__ lead_sum,
+    int64_t *__restrict__ lead_min, int64_t *__restrict__ lead_max) {
+    __shared__ uint32_t wsc[SEG_B / 64];
+
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const uint64_t tbase = (uint64_t)blockIdx.x * TILE;
+    const uint64_t c0g = tbase + (uint64_t)t * SEG_IPT; /* chunk start, global */
+    const uint64_t chunk_id = (uint64_t)blockIdx.x * SEG_B + t;
+
+    uint64_t kk[SEG_IPT], sv[SEG_IPT];
+    if (c0g + SEG_IPT <= n) { /* interior chunk: unguarded 16-B vector loads */
+        if (PK) {
+            const ulonglong2 *rp = reinterpret_cast<const ulonglong2 *>(k) + c0g;
+#pragma unroll
+            for (int j = 0; j < SEG_IPT; ++j) {
+                ulonglong2 r2 = rp[j];
+                kk[j] = r2.x;
+                sv[j] = r2.y;
+            }
+        } else {
+            const ulonglong2 *kp = reinterpret_cast<const ulonglong2 *>(k + c0g);
+            const ulonglong2 *vp = reinterpret_cast<const ulonglong2 *>(v + c0g);
+#pragma unroll
+            for (int j2 = 0; j2 < SEG_IPT / 2; ++j2) {
+                ulonglong2 t2 = kp[j2];
+                ulonglong2 u2 = vp[j2];
+                kk[2 * j2] = t2.x;
+                kk[2 * j2 + 1] = t2.y;
+                sv[2 * j2] = u2.x;
+                sv[2 * j2 + 1] = u2.y;
+            }
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < SEG_IPT; ++j) {
+            uint64_t gi = c0g + j;
+            kk[j] = (gi < n) ? k[PK ? 2 * gi : gi] : ~0ULL;
+            sv[j] = (gi < n) ? (PK ? k[2 * gi + 1] : v[gi]) : 0;
+        }
+    }
+    uint64_t prev = (c0g > 0 && c0g <= n) ? k[PK ? 2 * (c0g - 1) : c0g - 1] : 0;
+
+    /* count heads in the chunk */
+    uint32_t cnt = 0;
+#pragma unroll
+    for (int j = 0; j < SEG_IPT; ++j) {
+        uint64_t gi = c0g + j;
+        if (gi < n) {
+            uint64_t pk = (j > 0) ? kk[j - 1] : prev;
+            cnt += (gi == 0) || (kk[j] != pk);
+        }
+    }
+    /* block exclusive scan of cnt */
+    uint32_t inc = cnt;
+    for (int off = 1; off < 64; off <<= 1) {
+        uint32_t u = __shfl_up(inc, off);
+        if (lane >= off) inc += u;
+    }
+    if (lane == 63) wsc[w] = inc;
+    __syncthreads();
+    uint32_t excl = inc - cnt;
+    for (int i = 0; i < w; ++i) excl += wsc[i];
+
+    if (c0g >= n) { /* a chunk behind the rows */
+        lead_seg[chunk_id] = 0xFFFFFFFFu;
+        return;
+    }
+    int64_t segid = (int64_t)head_base[(size_t)blockIdx.x * hstride] + excl - 1;
+
+    /* A fully-distinct interior chunk emits its length-1 runs (1, 0.0 + v, v,
+     * v) with pure vector stores. If its last run goes on, the next chunk's
+     * lead carries the rest. */
+    if (cnt == SEG_IPT && c0g + SEG_IPT <= n) {
+        auto s1 = [&](int j) -> uint64_t {
+            double acc = 0.0;
+            acc += __longlong_as_double((long long)sv[j]);
+            return (uint64_t)__double_as_longlong(acc);
+        };
+        const int64_t s0 = segid + 1;
+        if ((s0 & 1) == 0) {
+            ulonglong2 *ok2 = (ulonglong2 *)(out_k + s0);
+            ulonglong2 *oc2 = (ulonglong2 *)(out_count + s0);
+            ulonglong2 *os2 = (ulonglong2 *)(out_sum + s0);
+            ulonglong2 *on2 = (ulonglong2 *)(out_min + s0);
+            ulonglong2 *ox2 = (ulonglong2 *)(out_max + s0);
+#pragma unroll
+            for (int j = 0; j < SEG_IPT / 2; ++j) {
+                ulonglong2 v2 = make_ulonglong2(sv[2 * j], sv[2 * j + 1]);
+                ok2[j] = make_ulonglong2(kk[2 * j], kk[2 * j + 1]);
+                oc2[j] = make_ulonglong2(1, 1);
+                os2[j] = make_ulonglong2(s1(2 * j), s1(2 * j + 1));
+                on2[j] = v2;
+                ox2[j] = v2;
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < SEG_IPT; ++j) {
+                out_k[s0 + j] = (int64_t)kk[j];
+                out_count[s0 + j] = 1;
+                ((uint64_t *)out_sum)[s0 + j] = s1(j);
+                out_min[s0 + j] = sv[j];
+                out_max[s0 + j] = sv[j];
+            }
+        }
+        lead_seg[chunk_id] = 0xFFFFFFFFu;
+        return;
+    }
+
+    const int64_t open_seg = segid; /* run open at chunk start */
+    StatsAccF64 lead, acc;
+    lead.reset();
+    acc.reset();
+    bool seen = false; /* a head has been met: acc belongs to a run started here */
+    auto store = [&](int64_t sid, const StatsAccF64 &a) {
+        out_count[sid] = (int64_t)a.cnt;
+        out_sum[sid] = a.sum;
+        out_min[sid] = vega_f64_ord((uint64_t)a.mn);
+        out_max[sid] = vega_f64_ord((uint64_t)a.mx);
+    };
+#pragma unroll
+    for (int j = 0; j < SEG_IPT; ++j) {
+        uint64_t gi = c0g + j;
+        if (gi < n) {
+            uint64_t pk = (j > 0) ? kk[j - 1] : prev;
+            if (gi == 0 || kk[j] != pk) {
+                if (seen) store(segid, acc); /* interior run: complete */
+                segid++;
+                out_k[segid] = (int64_t)kk[j];
+                acc.reset();
+                seen = true;
+            }
+            if (seen) acc.add(sv[j]);
+            else lead.add(sv[j]);
+        }
+    }
+    /* last run started here: what it has so far */
+    if (seen) store(segid, acc);
+    /* row c0g is valid: it is either a head or the lead */
+    if (c0g != 0 && kk[0] == prev) {
+        lead_seg[chunk_id] = (uint32_t)open_seg;
+        lead_cnt[chunk_id] = lead.cnt;
+        lead_sum[chunk_id] = lead.sum;
+        lead_min[chunk_id] = lead.mn;
+        lead_max[chunk_id] = lead.mx;
+    } else {
+        lead_seg[chunk_id] = 0xFFFFFFFFu;
+    }
+}
+
+/* k_seg_lead_fold for the f64 combiner's count, min and max: equal lead_seg
+ * values are combined within the wave, the last lane of each group adds the
+ * count with one integer atomic and folds min / max with f64_slot_extreme.
+ * All three are exact in any order. The sum is not touched here. */
+__global__ __launch_bounds__(BLOCK) void k_stats_f64_fold(
+    const uint32_t *__restrict__ lead_seg, const uint32_t *__restrict__ lead_cnt,
+    const int64_t *__restrict__ lead_min, const int64_t *__restrict__ lead_max,
+    uint64_t nchunks, int64_t *__restrict__ out_count, uint64_t *__restrict__ out_min,
+    uint64_t *__restrict__ out_max) {
+    const int lane = threadIdx.x & 63;
+    constexpr int U = SEG_FOLD_U;
+    const uint64_t stride = (uint64_t)gridDim.x * BLOCK * U;
+    /* block-uniform trip count: every lane takes part in the shuffles */
+    for (uint64_t c0 = (uint64_t)blockIdx.x * BLOCK * U; c0 < nchunks; c0 += stride) {
+        uint32_t sgs[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const uint64_t c = c0 + (uint64_t)u * BLOCK + threadIdx.x;
+            sgs[u] = (c < nchunks) ? lead_seg[c] : 0xFFFFFFFFu;
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const uint64_t c = c0 + (uint64_t)u * BLOCK + threadIdx.x;
+            const uint32_t sg = sgs[u];
+            const bool have = sg != 0xFFFFFFFFu;
+            if (!__any(have)) continue;
+            uint32_t ac = have ? lead_cnt[c] : 0;
+            int64_t an = have ? lead_min[c] : INT64_MAX;
+            int64_t ax = have ? lead_max[c] : INT64_MIN;
+            long long sid = have ? (long long)sg : -(long long)(lane + 2);
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1) {
+                long long s2 = __shfl_up(sid, off);
+                uint32_t c2 = __shfl_up(ac, off);
+                long long n2 = __shfl_up((long long)an, off);
+                long long x2 = __shfl_up((long long)ax, off);
+                if (lane >= off && s2 == sid) {
+                    ac += c2;
+                    an = (int64_t)n2 < an ? (int64_t)n2 : an;
+                    ax = (int64_t)x2 > ax ? (int64_t)x2 : ax;
+                }
+            }
+            long long snext = __shfl_down(sid, 1);
+            if (have && (lane == 63 || snext != sid)) {
+                atomicAdd((unsigned long long *)(out_count + sg), (unsigned long long)ac);
+                f64_slot_extreme<false>(out_min + sg, an);
+                f64_slot_extreme<true>(out_max + sg, ax);
+            }
+        }
+    }
+}
+
+/* lead_seg / lead_sum come out of the budget seg_reduce's leads have in
+ * ws_bytes_for. The three other lead arrays (20 B per chunk) go into `spare`,
+ * a buffer of spare_bytes the caller no longer needs (the grouping sort's idle
+ * ping-pong buffer, 16 B per row against 2.5 here), whenever it holds them —
+ * every n above a few hundred rows, on every grouping route — and into what
+ * is left of ws otherwise (n <= 1 or one partial tile: the slack covers it). */
+hipError_t seg_stats_f64(hipStream_t s, const uint64_t *k, const uint64_t *v, uint64_t n,
+                         int64_t *out_k, int64_t *out_count, double *out_sum,
+                         double *out_min, double *out_max, uint64_t *h_nout, Ws &ws,
+                         bool packed, const uint32_t *fin_heads, void *spare,
+                         size_t spare_bytes) {
+    if (n == 0) { *h_nout = 0; return hipSuccess; }
+    if (n >= (1ULL << 32)) return hipErrorNotSupported; /* u32 head scan limit */
+    uint32_t nb = nblocks_for(n);
+    uint64_t nchunks = (uint64_t)nb * SEG_B;
+    uint32_t *lead_seg = (uint32_t *)ws.take(nchunks * 4);
+    double *lead_sum = (double *)ws.take(nchunks * 8);
+    if (!lead_seg || !lead_sum) return hipErrorOutOfMemory;
+    const uint32_t *hc, *total_d;
+    uint32_t hstride;
+    HIP_TRY(seg_head_bases(s, k, n, packed, fin_heads, ws, &hc, &hstride, &total_d));
+    Ws sp(spare, spare ? spare_bytes : 0);
+    int64_t *lead_min = (int64_t *)sp.take(nchunks * 8);
+    int64_t *lead_max = (int64_t *)sp.take(nchunks * 8);
+    uint32_t *lead_cnt = (uint32_t *)sp.take(nchunks * 4);
+    if (!lead_min || !lead_max || !lead_cnt) {
+        /* rest starts where seg_head_bases' scan kept its transient partials
+         * (it scans through a copy of ws): safe only because those scan
+         * kernels precede k_seg_stats_f64 on the SAME stream */
+        Ws rest = ws;
+        lead_min = (int64_t *)rest.take(nchunks * 8);
+        lead_max = (int64_t *)rest.take(nchunks * 8);
+        lead_cnt = (uint32_t *)rest.take(nchunks * 4);
+        if (!lead_min || !lead_max || !lead_cnt) return hipErrorOutOfMemory;
+    }
+    uint32_t total = 0;
+    HIP_TRY(hipMemcpyAsync(&total, total_d, 4, hipMemcpyDeviceToHost, s));
+    {
+        ProfScope ps("seg_stats_f64", s);
+        if (packed)
+            hipLaunchKernelGGL((k_seg_stats_f64<true>), dim3(nb), dim3(SEG_B), 0, s, k, v, n, hc,
+                               hstride, out_k, out_count, out_sum, (uint64_t *)out_min,
+                               (uint64_t *)out_max, lead_seg, lead_cnt, lead_sum, lead_min,
+                               lead_max);
+        else
+            hipLaunchKernelGGL((k_seg_stats_f64<false>), dim3(nb), dim3(SEG_B), 0, s, k, v, n, hc,
+                               hstride, out_k, out_count, out_sum, (uint64_t *)out_min,
+                               (uint64_t *)out_max, lead_seg, lead_cnt, lead_sum, lead_min,
+                               lead_max);
+        HIP_TRY(hipGetLastError());
+    }
+    {
+        ProfScope ps("stats_f64_fold", s);
+        const uint64_t per = (uint64_t)BLOCK * SEG_FOLD_U; /* chunks per block and round */
+        const uint64_t rounds = (nchunks + per - 1) / per;
+        uint32_t gb = (uint32_t)(rounds < 4096 ? rounds : 4096); /* grid-stride beyond */
+        hipLaunchKernelGGL(k_stats_f64_fold, dim3(gb), dim3(BLOCK), 0, s, lead_seg, lead_cnt,
+                           lead_min, lead_max, nchunks, out_count, (uint64_t *)out_min,
+                           (uint64_t *)out_max);
+        HIP_TRY(hipGetLastError());
+    }
+    {
+        ProfScope ps("stats_f64_combine", s);
+        uint32_t gb = nb < 2048 ? nb : 2048;
+        hipLaunchKernelGGL(k_f64_seg_combine, dim3(gb), dim3(BLOCK), 0, s, lead_seg, lead_sum,
+                           nchunks, out_sum);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    *h_nout = total;
+    return hipSuccess;
+}
+
+/* grouping sort (as group_sort_reduce runs it) + seg_stats_f64; the sort
+ * reports its idle ping-pong buffer, which is handed on as spare */
+hipError_t group_sort_stats_f64(hipStream_t s, const uint64_t *in_k, const uint64_t *in_v,
+                                uint64_t n, int64_t *out_k, int64_t *out_count,
+                                double *out_sum, double *out_min, double *out_max,
+                                uint64_t *h_nout, Ws &ws) {
+    if (n == 0) { *h_nout = 0; return hipSuccess; }
+    const uint64_t *sk, *sv;
+    int pk = 0;
+    const uint32_t *fh = nullptr;
+    void *spare = nullptr;
+    size_t spare_bytes = 0;
+    hipError_t e = group_sort_u64(s, in_k, in_v, n, 0, nullptr, 1, &pk, ws, &sk, &sv, 0,
+                                  nullptr, &fh, &spare, &spare_bytes);
+    if (e != hipSuccess) return e;
+    return seg_stats_f64(s, sk, sv, n, out_k, out_count, out_sum, out_min, out_max, h_nout, ws,
+                         pk != 0, fh, spare, spare_bytes);
 }
 
 /* ------------------------------------------------------------------ */
@@ -4103,12 +4538,18 @@ __device__ __forceinline__ void load_pair(const uint64_t *col, uint64_t u, uint6
     }
 }
 
-/* OP: 0 SUM_I64, 2 SUM_F64, 3 MIN_I64, 4 MAX_I64 (column-wise; key column
- * always wrapping/ordered i64), COLRED_LEXMIN / COLRED_LEXMAX (row-wise) */
+/* OP: 0 SUM_I64, 2 SUM_F64, 3 MIN_I64, 4 MAX_I64, 5 MIN_F64, 6 MAX_F64
+ * (column-wise; key column always wrapping/ordered i64), COLRED_LEXMIN /
+ * COLRED_LEXMAX (row-wise). 5 / 6 keep the value accumulator as DOUBLE BITS
+ * and compare under vega_f64_ord with NaN as the identity, so rows and
+ * partials combine alike; the identity is the NaN the integer identity
+ * un-maps to, which is what a column of NaN reduces to. */
 template <int OP>
 __device__ __forceinline__ void cr_identity(uint64_t &k, uint64_t &v) {
     if (OP == 0) { k = 0; v = 0; }
     else if (OP == 2) { k = 0; v = 0x8000000000000000ULL; /* -0.0: x + -0.0 == x */ }
+    else if (OP == 5) { k = (uint64_t)INT64_MAX; v = vega_f64_ord((uint64_t)INT64_MAX); }
+    else if (OP == 6) { k = (uint64_t)INT64_MIN; v = vega_f64_ord((uint64_t)INT64_MIN); }
     else if (OP == 3 || OP == COLRED_LEXMIN) { k = (uint64_t)INT64_MAX; v = (uint64_t)INT64_MAX; }
     else { k = (uint64_t)INT64_MIN; v = (uint64_t)INT64_MIN; }
 }
@@ -4127,6 +4568,12 @@ __device__ __forceinline__ void cr_combine(uint64_t &k, uint64_t &v, uint64_t k2
     } else if (OP == 4) {
         if ((int64_t)k2 > (int64_t)k) k = k2;
         if ((int64_t)v2 > (int64_t)v) v = v2;
+    } else if (OP == 5) {
+        if ((int64_t)k2 < (int64_t)k) k = k2;
+        if (vega_f64_ord_or(v2, INT64_MAX) < vega_f64_ord_or(v, INT64_MAX)) v = v2;
+    } else if (OP == 6) {
+        if ((int64_t)k2 > (int64_t)k) k = k2;
+        if (vega_f64_ord_or(v2, INT64_MIN) > vega_f64_ord_or(v, INT64_MIN)) v = v2;
     } else if (OP == COLRED_LEXMIN) {
         if ((int64_t)k2 < (int64_t)k || (k2 == k && (int64_t)v2 < (int64_t)v)) { k = k2; v = v2; }
     } else {
@@ -4235,6 +4682,8 @@ hipError_t col_reduce(hipStream_t s, const int64_t *keys, const void *vals, uint
         case 2: HIP_TRY((col_reduce_launch<2>(s, k, v, n, grid, vec, pk, pv, out))); break;
         case 3: HIP_TRY((col_reduce_launch<3>(s, k, v, n, grid, vec, pk, pv, out))); break;
         case 4: HIP_TRY((col_reduce_launch<4>(s, k, v, n, grid, vec, pk, pv, out))); break;
+        case 5: HIP_TRY((col_reduce_launch<5>(s, k, v, n, grid, vec, pk, pv, out))); break;
+        case 6: HIP_TRY((col_reduce_launch<6>(s, k, v, n, grid, vec, pk, pv, out))); break;
         case COLRED_LEXMIN:
             HIP_TRY((col_reduce_launch<COLRED_LEXMIN>(s, k, v, n, grid, vec, pk, pv, out))); break;
         case COLRED_LEXMAX:

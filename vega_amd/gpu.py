@@ -23,6 +23,9 @@ OP_COUNT = 1
 OP_SUM_F64 = 2
 OP_MIN_I64 = 3
 OP_MAX_I64 = 4
+OP_MIN_F64 = 5  # f64 min / max: order of f64_order_key, NaN skipped
+OP_MAX_F64 = 6
+F64_OPS = (OP_SUM_F64, OP_MIN_F64, OP_MAX_F64)  # f64 values in, f64 values out
 
 STAT_COUNT = 0
 STAT_SUM = 1
@@ -74,6 +77,8 @@ def lib():
         _lib.vega_dev_ws_bytes.restype = ctypes.c_size_t
         _lib.vega_dev_ws_bytes.argtypes = [ctypes.c_uint64]
         _lib.vega_gpu_last_error.restype = ctypes.c_char_p
+        _lib.vega_f64_order_key.restype = ctypes.c_uint64
+        _lib.vega_f64_order_key.argtypes = [ctypes.c_uint64]
     return _lib
 
 
@@ -167,7 +172,17 @@ class Rdd:
                                             ctypes.byref(out)),
                "reduce_by_key", self.ctx._c)
         return Rdd(self.ctx, out.value,
-                   np.float64 if op == OP_SUM_F64 else np.int64)
+                   np.float64 if op in F64_OPS else np.int64)
+
+    def stats_by_key_f64(self, nparts=256):
+        """the f64 combiner: per key (count, sum, min, max) over f64 values
+        from one grouping sort; sum bit-identical to reduce_by_key(OP_SUM_F64),
+        min / max as OP_MIN_F64 / OP_MAX_F64"""
+        out = ctypes.c_uint64()
+        _check(lib().vega_gpu_stats_by_key_f64(self.ctx._c, ctypes.c_uint64(self.h),
+                                               ctypes.c_uint32(nparts), ctypes.byref(out)),
+               "stats_by_key_f64", self.ctx._c)
+        return StatsF64Rdd(self.ctx, out.value)
 
     def stats_by_key(self, nparts=256):
         """combine_by_key (pair_rdd.rs:20-33) with C = (count, sum, min, max)
@@ -376,7 +391,7 @@ class Rdd:
 
     # --- device-side actions (rdd.rs:274-322, :534-620, :1073-1153) ---
     def _vbox(self, op=None):
-        f64 = (op == OP_SUM_F64) if op is not None else self.vdtype == np.float64
+        f64 = (op in F64_OPS) if op is not None else self.vdtype == np.float64
         return ctypes.c_double() if f64 else ctypes.c_int64()
 
     def reduce(self, op=OP_SUM_I64):
@@ -394,7 +409,7 @@ class Rdd:
         """fold (rdd.rs:311-322): init combined nparts+1 times with reduce"""
         k = ctypes.c_int64()
         v = self._vbox(op)
-        iv = ctypes.c_double(init_v) if op == OP_SUM_F64 else ctypes.c_int64(init_v)
+        iv = ctypes.c_double(init_v) if op in F64_OPS else ctypes.c_int64(init_v)
         _check(lib().vega_gpu_fold(self.ctx._c, ctypes.c_uint64(self.h),
                                    ctypes.c_int(op), ctypes.c_int64(init_k),
                                    ctypes.byref(iv), ctypes.byref(k), ctypes.byref(v)),
@@ -565,6 +580,62 @@ class StatsRdd:
         lib().vega_gpu_free_rdd(self.ctx._c, ctypes.c_uint64(self.h))
 
 
+class StatsF64Rdd:
+    """result of Rdd.stats_by_key_f64: per key (count i64, sum, min, max f64)"""
+
+    def __init__(self, ctx, handle):
+        self.ctx = ctx
+        self.h = handle
+
+    def count(self):
+        """number of keys"""
+        n = ctypes.c_uint64()
+        _check(lib().vega_gpu_count(self.ctx._c, ctypes.c_uint64(self.h),
+                                    ctypes.byref(n)), "count", self.ctx._c)
+        return n.value
+
+    def collect(self):
+        """(keys i64, count i64, sum f64, min f64, max f64), rows aligned"""
+        n = ctypes.c_uint64(0)
+        _check(lib().vega_gpu_collect_stats_f64(self.ctx._c, ctypes.c_uint64(self.h),
+                                                None, None, None, None, None,
+                                                ctypes.byref(n)),
+               "collect_stats_f64 size", self.ctx._c)
+        cols = [np.empty(n.value, dtype=np.int64) for _ in range(2)] + [
+            np.empty(n.value, dtype=np.float64) for _ in range(3)]
+        _check(lib().vega_gpu_collect_stats_f64(self.ctx._c, ctypes.c_uint64(self.h),
+                                                *[_pp(a) for a in cols], ctypes.byref(n)),
+               "collect_stats_f64", self.ctx._c)
+        return tuple(a[:n.value] for a in cols)
+
+    def column(self, which):
+        """map_values(|c| c.<which>): a plain (key, column) Rdd (device copy);
+        the count is i64-valued, sum / min / max f64-valued"""
+        out = ctypes.c_uint64()
+        _check(lib().vega_gpu_stats_column(self.ctx._c, ctypes.c_uint64(self.h),
+                                           ctypes.c_int(which), ctypes.byref(out)),
+               "stats_column", self.ctx._c)
+        return Rdd(self.ctx, out.value, np.int64 if which == STAT_COUNT else np.float64)
+
+    def free(self):
+        lib().vega_gpu_free_rdd(self.ctx._c, ctypes.c_uint64(self.h))
+
+
+def f64_order_key(a):
+    """the order key of each element of a, as int64: the signed order MIN_F64 /
+    MAX_F64 compare by. a is a float64 array, or a uint64 / int64 array of bit
+    patterns (any other dtype: TypeError). Host only; it calls the exported
+    vega_f64_order_key once per element — meant for checks and small arrays,
+    not for columns."""
+    a = np.ascontiguousarray(a)
+    if a.dtype not in (np.float64, np.uint64, np.int64):
+        raise TypeError(f"f64_order_key: float64, uint64 or int64 expected, not {a.dtype}")
+    bits = a.view(np.uint64)
+    fn = lib().vega_f64_order_key
+    out = np.fromiter((fn(int(b)) for b in bits.ravel()), dtype=np.uint64, count=bits.size)
+    return out.view(np.int64).reshape(bits.shape)
+
+
 # ---------------- device-pointer API over torch tensors ----------------
 
 def _t(t):
@@ -648,6 +719,20 @@ def dev_sort_stats(keys_t, vals_t, out_k, out_count, out_sum, out_min, out_max, 
                                          ctypes.byref(nout),
                                          _t(ws_t), ctypes.c_size_t(ws_t.numel())),
            "dev_sort_stats")
+    return nout.value
+
+
+def dev_sort_stats_f64(keys_t, vals_t, out_k, out_count, out_sum, out_min, out_max, ws_t):
+    """dev_sort_stats for f64 values: out_k / out_count int64, out_sum / out_min /
+    out_max float64, n rows each; returns the number of keys"""
+    n = keys_t.numel()
+    nout = ctypes.c_uint64()
+    _check(lib().vega_dev_sort_stats_f64(_stream(), _t(keys_t), _t(vals_t),
+                                         ctypes.c_uint64(n), _t(out_k), _t(out_count),
+                                         _t(out_sum), _t(out_min), _t(out_max),
+                                         ctypes.byref(nout),
+                                         _t(ws_t), ctypes.c_size_t(ws_t.numel())),
+           "dev_sort_stats_f64")
     return nout.value
 
 
@@ -795,7 +880,7 @@ def dev_reduce_pairs(keys_t, vals_t, op, ws_t=None):
     if ws_t is None:
         ws_t = torch.empty(1 << 16, dtype=torch.uint8, device=keys_t.device)
     k = ctypes.c_int64()
-    v = ctypes.c_double() if op == OP_SUM_F64 else ctypes.c_int64()
+    v = ctypes.c_double() if op in F64_OPS else ctypes.c_int64()
     _check(lib().vega_dev_reduce_pairs(
         _stream(), _t(keys_t), _t(vals_t), ctypes.c_uint64(keys_t.numel()),
         ctypes.c_int(op), ctypes.byref(k), ctypes.byref(v),

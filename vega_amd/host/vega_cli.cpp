@@ -13,8 +13,10 @@
  * fallback anywhere in the product path.
  */
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <limits>
 #include <map>
 #include <vector>
 
@@ -319,6 +321,54 @@ int main(int argc, char **argv) {
             auto mx = st.column(VEGA_STAT_MAX);
             CHECK_EQ(sorted(mx.collect()), (pairs_t{{-1, 100}, {3, 4}, {7, 5}, {11, 0}}),
                      "stats_column(MAX) is a plain pair rdd");
+        }
+        /* stats_by_key_f64: the same combiner over f64 values; expected rows
+         * written out by hand (sums exact in any order). Key 3 holds only
+         * zeros: min is -0.0, max +0.0. Key 7 holds a NaN, which min and max
+         * skip and count counts. */
+        {
+            const double nan = std::numeric_limits<double>::quiet_NaN();
+            std::vector<std::pair<int64_t, double>> in{
+                {7, 0.5}, {3, 0.0}, {7, nan}, {3, -0.0}, {7, -2.25}, {11, 1e300}, {-1, -4.0}};
+            auto st = sc.make_rdd_f64(in, 3).stats_by_key_f64(3);
+            auto got = st.collect();
+            std::sort(got.begin(), got.end());
+            CHECK_EQ(got.size(), (size_t)4, "stats_by_key_f64 one row per key");
+            if (got.size() == 4) {
+                CHECK_EQ(got[0], (vega::KeyStatsF64{-1, 1, -4.0, -4.0, -4.0}),
+                         "stats_by_key_f64 single row");
+                CHECK_EQ(got[1], (vega::KeyStatsF64{3, 2, 0.0, -0.0, 0.0}),
+                         "stats_by_key_f64 orders -0.0 below +0.0");
+                CHECK_EQ(got[2].count == 3 && std::isnan(got[2].sum) && got[2].min == -2.25 &&
+                             got[2].max == 0.5, true,
+                         "stats_by_key_f64 counts a NaN row, min / max skip it");
+                CHECK_EQ(got[3], (vega::KeyStatsF64{11, 1, 1e300, 1e300, 1e300}),
+                         "stats_by_key_f64 large value");
+            }
+            CHECK_EQ(st.count(), (uint64_t)4, "stats_by_key_f64 count == #keys");
+        }
+        /* reduce_by_key with the f64 order ops, expected rows written by hand */
+        {
+            const double nan = std::numeric_limits<double>::quiet_NaN();
+            const double inf = std::numeric_limits<double>::infinity();
+            using frows_t = std::vector<std::pair<int64_t, double>>;
+            frows_t in{{1, 2.5}, {2, -inf}, {1, nan}, {2, inf}, {1, -7.0}, {5, 5e-324}};
+            auto r = sc.make_rdd_f64(in, 2);
+            auto mn = r.reduce_by_key(VEGA_OP_MIN_F64, 2).collect_f64();
+            auto mx = r.reduce_by_key(VEGA_OP_MAX_F64, 2).collect_f64();
+            std::sort(mn.begin(), mn.end());
+            std::sort(mx.begin(), mx.end());
+            CHECK_EQ(mn, (frows_t{{1, -7.0}, {2, -inf}, {5, 5e-324}}),
+                     "reduce_by_key(MIN_F64) hand-written");
+            CHECK_EQ(mx, (frows_t{{1, 2.5}, {2, inf}, {5, 5e-324}}),
+                     "reduce_by_key(MAX_F64) hand-written");
+            /* column-wise reduce / fold: key column i64, value column f64, NaN skipped */
+            using frow_t = vega::PairRdd::frow_t;
+            CHECK_EQ(r.reduce_f64(VEGA_OP_MIN_F64).value(), (frow_t{1, -inf}), "reduce(MIN_F64)");
+            CHECK_EQ(r.reduce_f64(VEGA_OP_MAX_F64).value(), (frow_t{5, inf}), "reduce(MAX_F64)");
+            CHECK_EQ(r.fold_f64({0, nan}, VEGA_OP_MIN_F64), (frow_t{0, -inf}),
+                     "fold(MIN_F64) skips a NaN init");
+            CHECK_EQ(r.fold_f64({9, 1e308}, VEGA_OP_MAX_F64), (frow_t{9, inf}), "fold(MAX_F64)");
         }
         /* randomized reduce vs in-binary std::map (datagen formula inline) */
         {

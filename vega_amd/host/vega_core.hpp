@@ -16,6 +16,7 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <cstring>
 #include <optional>
 #include <random>
 #include <stdexcept>
@@ -90,6 +91,58 @@ class StatsRdd {
     vega_rdd_t h_ = 0;
 };
 
+/* one row of stats_by_key_f64: count is i64, sum / min / max are doubles */
+struct KeyStatsF64 {
+    int64_t key, count;
+    double sum, min, max;
+    /* bit equality: tells -0.0 from +0.0, and a NaN equals the same NaN */
+    bool operator==(const KeyStatsF64 &o) const {
+        return key == o.key && count == o.count && memcmp(&sum, &o.sum, 8) == 0 &&
+               memcmp(&min, &o.min, 8) == 0 && memcmp(&max, &o.max, 8) == 0;
+    }
+    bool operator<(const KeyStatsF64 &o) const { return key < o.key; }
+};
+
+/* Rdd<(i64, (count, sum, min, max))> over f64 values — the result of
+ * PairRdd::stats_by_key_f64 */
+class StatsF64Rdd {
+  public:
+    StatsF64Rdd() = default;
+    StatsF64Rdd(vega_ctx_t *c, vega_rdd_t h) : c_(c), h_(h) {}
+
+    /* number of keys */
+    uint64_t count() const {
+        uint64_t n = 0;
+        check(vega_gpu_count(c_, h_, &n), "count", c_);
+        return n;
+    }
+    /* rows in grouping order (unspecified, as for reduce_by_key) */
+    std::vector<KeyStatsF64> collect() const {
+        uint64_t n = 0;
+        check(vega_gpu_collect_stats_f64(c_, h_, nullptr, nullptr, nullptr, nullptr, nullptr, &n),
+              "collect_stats_f64 size", c_);
+        std::vector<int64_t> k(n), cnt(n);
+        std::vector<double> sum(n), mn(n), mx(n);
+        if (n)
+            check(vega_gpu_collect_stats_f64(c_, h_, k.data(), cnt.data(), sum.data(), mn.data(),
+                                             mx.data(), &n), "collect_stats_f64", c_);
+        std::vector<KeyStatsF64> out(n);
+        for (uint64_t i = 0; i < n; i++) out[i] = {k[i], cnt[i], sum[i], mn[i], mx[i]};
+        return out;
+    }
+    /* map_values(|c| c.<which>): a plain pair rdd, f64-valued except the count */
+    inline PairRdd column(vega_stat_t which) const;
+    void free() {
+        if (c_ && h_) vega_gpu_free_rdd(c_, h_);
+        h_ = 0;
+    }
+    vega_rdd_t handle() const { return h_; }
+
+  private:
+    vega_ctx_t *c_ = nullptr;
+    vega_rdd_t h_ = 0;
+};
+
 /* Rdd<(i64, i64|f64)> — handle + the PairRdd method surface */
 class PairRdd {
   public:
@@ -100,13 +153,21 @@ class PairRdd {
     PairRdd reduce_by_key(vega_op_t op = VEGA_OP_SUM_I64, uint32_t num_splits = 256) const {
         vega_rdd_t out = 0;
         check(vega_gpu_reduce_by_key(c_, h_, op, num_splits, &out), "reduce_by_key", c_);
-        return PairRdd(c_, out, op == VEGA_OP_SUM_F64);
+        return PairRdd(c_, out, op == VEGA_OP_SUM_F64 || op == VEGA_OP_MIN_F64 ||
+                                    op == VEGA_OP_MAX_F64);
     }
     /* pair_rdd.rs:20-33 combine_by_key with C = (count, sum, min, max) */
     StatsRdd stats_by_key(uint32_t num_splits = 256) const {
         vega_rdd_t out = 0;
         check(vega_gpu_stats_by_key(c_, h_, num_splits, &out), "stats_by_key", c_);
         return StatsRdd(c_, out);
+    }
+    /* the same over f64 values: IEEE sum in reduce_by_key(SUM_F64)'s summation
+     * shape, min / max as VEGA_OP_MIN_F64 / MAX_F64 (NaN skipped) */
+    StatsF64Rdd stats_by_key_f64(uint32_t num_splits = 256) const {
+        vega_rdd_t out = 0;
+        check(vega_gpu_stats_by_key_f64(c_, h_, num_splits, &out), "stats_by_key_f64", c_);
+        return StatsF64Rdd(c_, out);
     }
     /* pair_rdd.rs:35-52; group sizes (full groups: sort_by_key + scan host-side) */
     PairRdd group_by_key_count(uint32_t num_splits = 256) const {
@@ -241,6 +302,22 @@ class PairRdd {
         check(vega_gpu_fold(c_, h_, op, init.first, &init.second, &k, &v), "fold", c_);
         return {k, v};
     }
+    /* the same on (i64, f64) rows, for the f64 ops (SUM_F64, MIN_F64, MAX_F64):
+     * the value comes back, and init goes in, as a double */
+    using frow_t = std::pair<int64_t, double>;
+    std::optional<frow_t> reduce_f64(vega_op_t op = VEGA_OP_SUM_F64) const {
+        int64_t k = 0;
+        double v = 0;
+        int ne = 0;
+        check(vega_gpu_reduce(c_, h_, op, &k, &v, &ne), "reduce", c_);
+        return ne ? std::optional<frow_t>(frow_t{k, v}) : std::nullopt;
+    }
+    frow_t fold_f64(frow_t init, vega_op_t op = VEGA_OP_SUM_F64) const {
+        int64_t k = 0;
+        double v = 0;
+        check(vega_gpu_fold(c_, h_, op, init.first, &init.second, &k, &v), "fold", c_);
+        return {k, v};
+    }
     /* aggregate(init, seq, comb) collapses to fold under the fixed op enum */
     row_t aggregate(row_t init, vega_op_t op = VEGA_OP_SUM_I64) const { return fold(init, op); }
     /* rdd.rs:1081-1099: lexicographic (Ord for (i64, i64)) extremes */
@@ -352,6 +429,12 @@ inline PairRdd StatsRdd::column(vega_stat_t which) const {
     return PairRdd(c_, out, false);
 }
 
+inline PairRdd StatsF64Rdd::column(vega_stat_t which) const {
+    vega_rdd_t out = 0;
+    check(vega_gpu_stats_column(c_, h_, which, &out), "stats_column", c_);
+    return PairRdd(c_, out, which != VEGA_STAT_COUNT);
+}
+
 /* Context::new (context.rs:147-164); local mode, one GPU per process */
 class Context {
   public:
@@ -375,6 +458,16 @@ class Context {
     PairRdd make_rdd(const std::vector<std::pair<int64_t, int64_t>> &data,
                      uint32_t num_splits) {
         return parallelize(data, num_splits);
+    }
+    PairRdd make_rdd_f64(const std::vector<std::pair<int64_t, double>> &data,
+                         uint32_t num_splits) {
+        std::vector<int64_t> k(data.size());
+        std::vector<double> v(data.size());
+        for (size_t i = 0; i < data.size(); i++) { k[i] = data[i].first; v[i] = data[i].second; }
+        vega_rdd_t h = 0;
+        check(vega_gpu_make_rdd_f64(c_, k.data(), v.data(), data.size(), num_splits, &h),
+              "make_rdd_f64", c_);
+        return PairRdd(c_, h, true);
     }
     PairRdd gen_uniform(uint64_t n, uint64_t seed, int key_bits, uint64_t start = 0,
                         uint32_t num_splits = 256) {
